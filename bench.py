@@ -5,13 +5,27 @@ GPU, the flat gradient buffer all-reduced over RCCL in two buckets per step: coa
 ends, fine net + loss after the fine backward).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--path engine|dropin] [--precision fp32|bf16]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds the scene, runs W warm-up steps, times K steps,
+writes the outputs of the last timed step if --dump-outputs is given, and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).  Every other record listed below
+(roofline, the other precision, psnr, dp diagnostics, llff, sweep, ngp, container, cpu_baseline, dropin beside the
+engine, the fp32-MFMA reference leg) takes runs of its own and is measured only with --full; there the --no-* options
+drop single legs.  `final_loss` is read when the engine leg ends: the loss of the last timed step in a plain run, of
+the last roofline-pass step (--timing-steps later) with --full.
+
+--dump-outputs DIR writes what the timed path left after its last timed step, as float32 DIR/<name>.npy: `loss` (the
+value step() returns), `params` (the flat parameter buffer after the step's Adam update: coarse net, then fine net)
+and `grads` (the step's gradient buffer, same layout).  Scene, initial weights, ray batches and
+sampling seeds are all seeded, so the same arguments give the same inputs in every run and build.
 
 With --gpus N > 1 and no torchrun environment, bench.py starts `torch.distributed.run` with N ranks itself
 (before any GPU call) and exits with its status; under the driver's own torchrun it runs as one rank.
 Weak scaling (default): 4096 rays per GPU per step.  --strong: 4096 rays per step in total, each rank taking
 the rank-strided slice of the same global draw (an/scripts/create_clusters.py:799).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0; with --full it also carries
   roofline      — the dominant kernel class of the fine net's trunk GEMMs: the class (fwd / dgrad / wgrad)
                   with the largest mean launch time.  Durations are HIP events the library records on the
                   launch stream in --timing-steps (default 3) extra steps AFTER the timed region, run with
@@ -75,6 +89,9 @@ HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E peak
 MAC_PER_EVAL = 500864
 FLOP_PER_RAY = 769327104       # 6*MAC*(64 coarse + 192 fine evaluations), SURVEY.md §8(d)
 K256 = [1, 2, 3, 5, 6, 7]      # trunk layers with a 256x256 weight (trunk.0: K=63, trunk.4: K=319)
+# the legs beside the headline figure: each has a --no-<leg> option and runs only with --full
+LEGS = ("cpu_baseline", "dropin", "psnr", "other_precision", "llff", "sweep", "ngp", "container", "native_ref")
+DUMP_BYTES_MAX = 64 * 10**6    # --dump-outputs: all files together
 
 
 _T0 = time.perf_counter()
@@ -146,7 +163,20 @@ def parse():
                     help="CPU-oracle sample of the ngp / container sub-records (seconds)")
     ap.add_argument("--no-native-ref", action="store_true",
                     help="skip the fp32-MFMA (native) engine leg timed beside the split-GEMM engine")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, measure every other record of the line (roofline pass, other "
+                         "precision, drop-in path, fp32-MFMA leg, dp diagnostics, llff, psnr, sweep, ngp, container, "
+                         "cpu_baseline); the --no-* options drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left (loss, params, grads) as float32 "
+                         "DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:   # a plain run: the headline path's warm-up and timed steps, nothing else
+        for leg in LEGS:
+            setattr(a, "no_" + leg, True)
+    return a
 
 
 def _free_port():
@@ -266,7 +296,7 @@ def cpu_baseline(S, NI, n, steps, world=1):
     return rec
 
 
-def dropin_run(rb, dev, a, world, rank, n_local, precision="fp32", amp_dtype=torch.float16):
+def dropin_run(rb, dev, a, world, rank, n_local, precision="fp32", amp_dtype=torch.float16, capture=None):
     """The reference loop body (runtime_adapt.py:286-310) on the drop-in surface: HierarchicalNeRF (coarse +
     fine VanillaNeRF, autograd through the HIP MLP / compositing / sampling ops) -> compute_mse_loss (coarse +
     fine terms) -> backward -> clip_grad_norm_(1.0) -> torch.optim.Adam ('sigma' / 'color' groups).  precision
@@ -311,6 +341,11 @@ def dropin_run(rb, dev, a, world, rank, n_local, precision="fp32", amp_dtype=tor
         loss = one(s)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if capture is not None:   # --dump-outputs: the last timed step's loss, updated parameters and gradients
+        ps = [p for p in model.parameters() if p.grad is not None]
+        capture.update(loss=loss.detach().reshape(1).clone(),
+                       params=torch.cat([p.detach().float().reshape(-1) for p in ps]),
+                       grads=torch.cat([p.grad.detach().float().reshape(-1) for p in ps]))
     rec = {"value": round(n_local * a.steps / el, 1), "unit": "rays/s", "ms_per_step": round(el / a.steps * 1e3, 3),
            "final_loss": round(float(loss.item()), 6), "optimizer": kind,
            "path": "render_rays + HierarchicalNeRF(VanillaNeRF x2) autograd + compute_mse_loss + "
@@ -453,9 +488,11 @@ def roofline(tm, bf16, overlap, bf16_flags=0, split=False):
     return roof
 
 
-def engine_run(a, dev, rb, world, rank, n_local, precision, barrier, nccl, fp32_gemm=None):
-    """The fused train step (NeRFTrainer) timed over a.steps after a.warmup: value, ms/step, the live-event roofline,
-    and (N > 1) the per-rank exchange diagnostics.  Returns (record, trainer, (coarse, fine))."""
+def engine_run(a, dev, rb, world, rank, n_local, precision, barrier, nccl, fp32_gemm=None, capture=None):
+    """The fused train step (NeRFTrainer) timed over a.steps after a.warmup: value, ms/step and, with a.full, the
+    live-event roofline and (N > 1) the per-rank exchange diagnostics, each from extra steps after the timed region.
+    ``capture`` (a dict, --dump-outputs) receives copies of what the last timed step left.
+    Returns (record, trainer, (coarse, fine))."""
     from nerf_amd.trainer import NeRFTrainer
     from nerf_amd.vanilla import VanillaNeRF
     torch.manual_seed(0)   # the same initial weights for every precision (the PSNR comparison starts from them)
@@ -480,22 +517,32 @@ def engine_run(a, dev, rb, world, rank, n_local, precision, barrier, nccl, fp32_
     barrier()
     torch.cuda.synchronize()
     el_local = time.perf_counter() - t0
-    # the roofline pass: timing_steps more steps (outside the timed region) with every launch alone on the device —
-    # the coarse backward back on the main stream, the fine weight gradients back in line — and HIP events around the
-    # fine net's trunk GEMMs, so each kernel class's mean launch time is its own (the production step runs them
-    # concurrently on three streams, where a launch's wall time is shared)
+    if capture is not None:   # --dump-outputs: loss_buf is a view of the gradient buffer the next step zeroes
+        capture.update(loss=loss.detach().clone(), params=tr.params.detach().clone(), grads=tr.grads.detach().clone())
+    full = getattr(a, "full", True)
     n_ev = max(1, a.timing_steps)
-    conc = (tr.overlap, tr.split_wgrad)
-    tr.overlap, tr.split_wgrad = False, False
-    tr.enable_timing(n_ev, skip=0)
-    for s in range(a.warmup + a.steps, a.warmup + a.steps + n_ev):
-        one(s)
-    torch.cuda.synchronize()
-    tr.overlap, tr.split_wgrad = conc
-    tm = tr.collect_timing()
+    tm = None
+    if full:
+        # the roofline pass: timing_steps more steps (outside the timed region) with every launch alone on the device —
+        # the coarse backward back on the main stream, the fine weight gradients back in line — and HIP events around
+        # the fine net's trunk GEMMs, so each kernel class's mean launch time is its own (the production step runs them
+        # concurrently on three streams, where a launch's wall time is shared)
+        conc = (tr.overlap, tr.split_wgrad)
+        tr.overlap, tr.split_wgrad = False, False
+        tr.enable_timing(n_ev, skip=0)
+        for s in range(a.warmup + a.steps, a.warmup + a.steps + n_ev):
+            one(s)
+        torch.cuda.synchronize()
+        tr.overlap, tr.split_wgrad = conc
+        tm = tr.collect_timing()
     el = el_local
     dp = None
-    if world > 1:
+    if world > 1 and not full:   # the step time is the slowest rank's, as in the dp record
+        mine = torch.tensor([el_local], dtype=torch.float64, device=dev)
+        allr = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(allr, mine)
+        el = max(float(r.item()) for r in allr)
+    elif world > 1:
         # the exchange as it runs in production: a.timing_steps more steps with the side stream on and events around the
         # two buckets only (bucket 0 = coarse gradient on the side stream, bucket 1 = fine gradient + loss); the kernel
         # pass above ran without the side stream, i.e. with ONE all-reduce of the whole buffer (reported beside it)
@@ -530,11 +577,12 @@ def engine_run(a, dev, rb, world, rank, n_local, precision, barrier, nccl, fp32_
         dp.update(exposed_exchange(a, tr, one, dev, world, barrier, el / a.steps * 1e3))
     rec = {"value": round(n_local * world * a.steps / el, 1), "ms_per_step": round(el / a.steps * 1e3, 3),
            "final_loss": round(float(loss.item()), 6),
-           "roofline": dict(roofline(tm, precision == "bf16", False, tr.bf16_flags,
-                                     split=(tr.fp32_gemm if precision == "fp32" and tr.fp32_gemm != "native"
-                                            else False)), event_steps=n_ev,
-                            event_pass="the timing_steps steps after the timed region, every launch alone (no "
-                                       "side-stream coarse backward, fine weight gradients in line)"),
+           "roofline": None if tm is None else
+           dict(roofline(tm, precision == "bf16", False, tr.bf16_flags,
+                         split=(tr.fp32_gemm if precision == "fp32" and tr.fp32_gemm != "native" else False)),
+                event_steps=n_ev,
+                event_pass="the timing_steps steps after the timed region, every launch alone (no "
+                           "side-stream coarse backward, fine weight gradients in line)"),
            "streams": {"coarse_bwd_beside_fine_fwd": tr.overlap and tr.overlap_with == "fwd",
                        "coarse_bwd_beside_fine_bwd": tr.overlap and tr.overlap_with == "bwd", "fine_wgrad_stream": tr.split_wgrad}}
     if precision == "fp32":
@@ -547,6 +595,23 @@ def engine_run(a, dev, rb, world, rank, n_local, precision, barrier, nccl, fp32_
     if dp:
         rec["dp"] = dp
     return rec, tr, (coarse, fine)
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: each captured tensor as float32 ``path``/<name>.npy.  All files together stay under
+    DUMP_BYTES_MAX: an array over its equal share of the budget is written as a fixed sample (seed 0, sorted flat
+    indices, the same in every run), with the indices beside it as <name>_index.npy (float64 holds them exactly)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, t in arrays.items():
+        x = t.detach().to(torch.float32).reshape(-1).cpu()
+        if x.numel() * 4 > share:
+            k = (share - 256) // (4 + 8)   # 256: the two .npy headers
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            np.save(os.path.join(path, name + "_index.npy"), idx.numpy().astype(np.float64))
+            x = x[idx]
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
 
 
 def _snapshot(tr):
@@ -773,12 +838,19 @@ def main():
     runs = {}
     engine = None
     progress(f"rank {rank}/{world}: scene ready")
-    if a.path == "engine" or world == 1:
-        engine, tr, nets = engine_run(a, dev, rb, world, rank, n_local, a.precision, barrier, nccl)
+    dump = {} if a.dump_outputs else None   # filled by the headline path after its last timed step
+    if a.path == "engine" or (world == 1 and a.full):
+        engine, tr, nets = engine_run(a, dev, rb, world, rank, n_local, a.precision, barrier, nccl,
+                                      capture=dump if a.path == "engine" else None)
         runs[a.precision] = (tr, nets)
     drop = None
     if world == 1 and (a.path == "dropin" or not a.no_dropin):
-        drop = dropin_run(rb, dev, a, world, rank, n_local, a.precision)
+        drop = dropin_run(rb, dev, a, world, rank, n_local, a.precision,
+                          capture=dump if a.path == "dropin" else None)
+    if dump and rank == 0:
+        write_outputs(a.dump_outputs, dump)
+        progress(f"outputs of the last timed step written to {a.dump_outputs}")
+    dump = None
     sub = None
     if not a.no_other_precision and a.path == "engine":
         sub, tr2, nets2 = engine_run(a, dev, rb, world, rank, n_local, other, barrier, nccl)
@@ -805,7 +877,7 @@ def main():
                                (" [drop-in render_rays/autograd path]" if a.path == "dropin" else " [fused engine]"),
                    "global_batch": a.batch if a.strong else a.batch * world, "rays_per_gpu": n_local,
                    "samples": [a.samples, a.importance], "parallelism": f"dp{world}", "precision": a.precision,
-                   "path": a.path, "fp32_gemm": None if bf16 else a.fp32_gemm},
+                   "path": a.path, "fp32_gemm": None if bf16 else a.fp32_gemm, "full": a.full},
         "rccl_ranks": world, "backend": ("nccl (RCCL)" if nccl else "gloo (rehearsal)") if world > 1 else None,
         "roofline": engine["roofline"] if engine else None,
         "step_mfma_frac": round(value * FLOP_PER_RAY / world / 1e12 /

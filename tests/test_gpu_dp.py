@@ -227,7 +227,7 @@ def test_bench_engine_run_world2_gloo():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
            "--warmup", "1", "--train-views", "4", "--no-psnr", "--no-cpu-baseline", "--no-llff", "--no-sweep",
            "--no-dropin", "--no-other-precision", "--no-native-ref"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
@@ -256,7 +256,7 @@ def test_bench_world2_line_complete_gloo():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
            "--warmup", "1", "--timing-steps", "1", "--train-views", "4", "--psnr-steps", "8", "--psnr-views", "1",
            "--cpu-batch", "32", "--cpu-steps", "1", "--no-llff", "--no-sweep", "--no-dropin", "--no-other-precision",
            "--no-native-ref", "--container-steps", "3", "--container-warmup", "4", "--prod-cpu-seconds", "1"]

@@ -3,6 +3,7 @@
 # variants so that clock drift hits all of them.  Usage: VARIANTS="x6base x6even" ROUNDS=2 tools/ab_x6.sh
 set -o pipefail
 cd "$(dirname "$0")/.."
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"  # the roofline record printed below comes from the --full pass
 mkdir -p gpurun_out && export TMPDIR=/tmp
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in ${VARIANTS:-x6base}; do

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEP=${1:-all}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 20 --warmup 5"}
+BENCH_ARGS="--full ${BENCH_ARGS:-"--steps 20 --warmup 5"}"
 if [[ $STEP == all || $STEP == test ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; rc=$?
   tail -30 gpurun_out/pytest_gpu.log; [[ $rc -ne 0 ]] && exit $rc

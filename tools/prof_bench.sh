@@ -4,6 +4,7 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out && export TMPDIR=/tmp
 P=${PREC:-bf16}
+BENCH_ARGS="--full $BENCH_ARGS"  # the roofline pass and the legs the --no-* options below pare down
 timeout -k 10 300 python bench.py --precision $P --no-cpu-baseline --no-psnr $BENCH_ARGS > gpurun_out/b_$P.log 2>&1 || { tail -30 gpurun_out/b_$P.log; exit 1; }
 tail -1 gpurun_out/b_$P.log | cut -c1-3000
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$P -o run --output-format csv -- python3 bench.py --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-psnr --no-dropin --no-ngp --no-container $LEG_ARGS $BENCH_ARGS > gpurun_out/prof_$P.log 2>&1 || { tail -20 gpurun_out/prof_$P.log; exit 1; }

@@ -12,14 +12,14 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 $O/smoke.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 560 python bench.py > $O/bench_default.log 2>&1 || { tail -30 $O/bench_default.log; exit 1; }
+  timeout -k 10 560 python bench.py --full > $O/bench_default.log 2>&1 || { tail -30 $O/bench_default.log; exit 1; }
   tail -1 $O/bench_default.log | cut -c1-400
 fi
 [ -n "$STOP_AFTER_BENCH" ] && exit 0
 for P in ${SKIP_PROF:+none} ${SKIP_PROF:-fp32 bf16}; do
   [ "$P" = none ] && break
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$P -o run --output-format csv -- \
-    python3 bench.py --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-psnr --no-dropin --no-other-precision --no-native-ref --no-ngp --no-container ${LEG_ARGS---no-llff --no-sweep} \
+    python3 bench.py --full --precision $P --steps 20 --warmup 5 --no-cpu-baseline --no-psnr --no-dropin --no-other-precision --no-native-ref --no-ngp --no-container ${LEG_ARGS---no-llff --no-sweep} \
     > $O/prof_$P.log 2>&1 || { tail -20 $O/prof_$P.log; exit 1; }
   python3 tools/prof_summary.py $O/prof_$P/run_kernel_stats.csv 28 3 > $O/prof_${P}_summary.txt 2>&1
   python3 tools/step_timeline.py $O/prof_$P/run_kernel_trace.csv > $O/step_${P}.txt 2>&1 || true
@@ -54,7 +54,7 @@ fi
 # filter alone still faulted, 800 steps into the fp32 PSNR training)
 F="x6|gemm|bwd_layer|mlp_fwd_fused|tail|color_bwd|head_bwd|reduce_"
 timeout -s KILL 1000 rocprofv3 --kernel-include-regex "$F" --kernel-iteration-range "${PMC_ITER:-[1-100]}" --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE \
-  --kernel-trace --output-format csv -d $O/pmc_full -o run -- python3 bench.py > $O/pmc_full_bench.log 2>&1
+  --kernel-trace --output-format csv -d $O/pmc_full -o run -- python3 bench.py --full > $O/pmc_full_bench.log 2>&1
 rc=$?; echo "PMC pass over the full bench: rc=$rc"; tail -1 $O/pmc_full_bench.log | cut -c1-300
 python3 - <<'PY'
 import csv, glob

@@ -19,5 +19,5 @@ for mode in eager graph eager graph; do
 done
 fi
 [ -n "$NO_BENCH" ] && exit 0
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default_stderr.txt || { tail -30 $O/bench_default_stderr.txt; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default_stderr.txt || { tail -30 $O/bench_default_stderr.txt; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1]); print('C2', d['value'], d['ms_per_step'], 'C3', d['bf16']['value'], 'cont', d['container']['value'], 'ngp', d['ngp']['value'], 'roof', d['roofline']['frac'])"

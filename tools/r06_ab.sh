@@ -12,7 +12,7 @@ ARGS="--precision ${PREC:-bf16} --steps 30 --warmup 5 --no-cpu-baseline --no-psn
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in $A new; do
     if [ $v = new ]; then L=""; else L="NERF_AMD_LIB=ab/$v.so"; fi
-    env $L timeout -k 10 200 python bench.py $ARGS > $O/ab_${v}_$r.json 2> $O/ab_${v}_$r.err || { tail -20 $O/ab_${v}_$r.err; exit 1; }
+    env $L timeout -k 10 200 python bench.py --full $ARGS > $O/ab_${v}_$r.json 2> $O/ab_${v}_$r.err || { tail -20 $O/ab_${v}_$r.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/ab_${v}_$r.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$v', d['value'], d['ms_per_step'], r.get('class'), r.get('mean_launch_ms'), {k: v.get('mean_launch_ms') for k, v in r.get('classes', {}).items()})"
   done
 done

@@ -12,5 +12,5 @@ fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
 [ -n "$NO_BENCH" ] && exit 0
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default_stderr.txt || { tail -30 $O/bench_default_stderr.txt; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default_stderr.txt || { tail -30 $O/bench_default_stderr.txt; exit 1; }
 cut -c1-400 $O/bench_default.json

@@ -9,7 +9,7 @@ for r in 1 2 3; do
   for P in bf16 fp32; do
     for V in fwd bwd none; do
       F="--overlap-with $V"; [ $V = none ] && F="--no-overlap"
-      timeout -k 10 120 python3 bench.py --precision $P $A $F > $O/ov_${P}_${V}_$r.log 2>&1 || { tail -5 $O/ov_${P}_${V}_$r.log; exit 1; }
+      timeout -k 10 120 python3 bench.py --full --precision $P $A $F > $O/ov_${P}_${V}_$r.log 2>&1 || { tail -5 $O/ov_${P}_${V}_$r.log; exit 1; }
       echo "$P $V r$r $(tail -1 $O/ov_${P}_${V}_$r.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])')" | tee -a $O/overlap_ab.txt
     done
   done

@@ -8,7 +8,7 @@ A="--steps 50 --warmup 8 --no-cpu-baseline --no-psnr --no-dropin --no-other-prec
 for r in 1 2 3; do
   for V in default split_wgrad; do
     F=""; [ $V = split_wgrad ] && F="--split-wgrad"
-    timeout -k 10 120 python3 bench.py $A $F > $O/wg_${V}_$r.log 2>&1 || { tail -5 $O/wg_${V}_$r.log; exit 1; }
+    timeout -k 10 120 python3 bench.py --full $A $F > $O/wg_${V}_$r.log 2>&1 || { tail -5 $O/wg_${V}_$r.log; exit 1; }
     echo "fp32 $V r$r $(tail -1 $O/wg_${V}_$r.log | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])')" | tee -a $O/wg_ab.txt
   done
 done
