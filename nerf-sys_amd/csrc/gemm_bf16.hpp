@@ -595,9 +595,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_wsr_kernel(const nerf_bf1
   // epilogue stores per lane (bf16 outputs: one 16-B store per pair of 32-column halves; fp32: 4 per tile) plus the
   // ReLU bitmask word stores of the forward; they are younger than the DMA of the next STAGES - 1 slabs, and vmcnt
   // counts in issue order, so a wait that ignored them would drain the stores at every panel boundary
-#ifndef NERF_WSR_STORE_AWARE
-#define NERF_WSR_STORE_AWARE 1
-#endif
   // exact count only: an over-count would let a wait pass before its slab landed
   const int NST = TM * TN * (OUT_BF16 ? 2 : 4) + ((EPI == EPI_BIAS_RELU && mbits_out) ? TM * TN : 0);
   constexpr int NML = (EPI == EPI_MASK) ? TM * TN : 0;  // mask-word loads issued at each panel start
@@ -608,12 +605,10 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_bf16_wsr_kernel(const nerf_bf1
     // the DMA of the younger slabs, the epilogue stores of iterations g - STAGES + 1 .. g - 1 and the mask-word
     // loads of panel starts g - STAGES + 2 .. g - 1
     int extra = 0;
-    if (NERF_WSR_STORE_AWARE) {
 #pragma unroll
-      for (int e = 1; e <= STAGES - 1; ++e) {
-        if (g - e >= 0 && (g - e) % NK == NK - 1) extra += NST;
-        if (e <= STAGES - 2 && g - e >= 0 && (g - e) % NK == 0) extra += NML;
-      }
+    for (int e = 1; e <= STAGES - 1; ++e) {
+      if (g - e >= 0 && (g - e) % NK == NK - 1) extra += NST;
+      if (e <= STAGES - 2 && g - e >= 0 && (g - e) % NK == 0) extra += NML;
     }
     ntb_wait_vmcnt(younger * 2 + extra);
     __builtin_amdgcn_s_barrier();

@@ -9,8 +9,8 @@
 // (16 cycles per 16K MACs each) instead of sixteen `v_mfma_f32_16x16x4_f32` (8 cycles per 1K MACs each): 2.7x the
 // MAC rate of the fp32 matrix cores, which moves the 256x256 trunk layers from MFMA-bound to HBM-bound.
 //
-//   gemm_nt_x6     C[m][n] = epi( sum_k A[m][k] B[n][k] ): A fp32 activations (split while staged into LDS), B the
-//                  layer weights (forward) or their transpose (input gradient) as three pre-split bf16 planes
+//   gemm_nt_x6w    C[m][n] = epi( sum_k A[m][k] B[n][k] ): A fp32 activations (split in registers), B the layer
+//                  weights (forward) or their transpose (input gradient) as three pre-split bf16 planes
 //   gemm_wgrad_x6  P[s][n][k] = sum_{m in split s} G[m][n] X[m][k] (+ bias column sums): both operands fp32
 //                  activations, split while staged; fp32 slabs, deterministic reduce as in gemm.hpp
 // Fragment / LDS conventions are gemm_bf16.hpp's (NT: [rows][BK] tiles, ds_read_b128 per fragment, C^T so a lane
@@ -28,54 +28,11 @@ __device__ __forceinline__ uint32_t x6_pack(float a, float b) {
 }
 
 // four fp32 values -> their hi / mid / lo bf16 pieces, packed in pairs (v_cvt_pk_bf16_f32 rounds to nearest even).
-// DOT2: each residual x - piece by one v_dot2c_f32_bf16 against (-1, 0) / (0, -1) instead of widening the piece
-// (shift / mask) and a packed subtract: 7 VALU instructions per pair instead of 9, exact (the difference is an fp32
-// number), so the pieces are bitwise the same.  Measured (C2, profiles/r05/x6_variants_ab.txt): on every split kernel
-// forward 0.574 -> 0.566 ms, input gradient unchanged, weight gradient 0.479 -> 0.515 ms (its split sits in the staging
-// path, where the dot's longer latency shows); on the forward alone within the noise (C2 224.0-224.9k either way).
-// Off by default (NERF_X6_DOT2_FWD=1: the forward on the dot form).
-#ifndef NERF_X6_DOT2_FWD
-#define NERF_X6_DOT2_FWD 0
-#endif
-template <bool DOT2 = false>
+// Each residual is the fp32 value minus the widened piece (shift / mask, packed subtract: 9 VALU per pair).  A
+// v_dot2c_f32_bf16 form (7 VALU per pair, the same pieces) measured forward 0.574 -> 0.566 ms, input gradient
+// unchanged, weight gradient 0.479 -> 0.515 ms, and on the forward alone within the noise
+// (profiles/r05/x6_variants_ab.txt): not kept.
 __device__ __forceinline__ void x6_split4(const float4 v, uint2& h, uint2& m, uint2& l) {
-#ifdef NERF_X6_NOSPLIT  // ablation builds only: split cost probe (wrong results)
-  h = m = l = make_uint2(__float_as_uint(v.x), __float_as_uint(v.y));
-  return;
-#endif
-#ifdef NERF_X6_CHEAPSPLIT  // ablation builds only: the hi pieces as all three (realistic operand values, 1/5 of the
-  // split's VALU; wrong results) — does the split's VALU hold the kernels?
-  h = m = l = make_uint2(x6_pack(v.x, v.y), x6_pack(v.z, v.w));
-  return;
-#endif
-#ifdef NERF_X6_DOT2SPLIT  // A/B builds: every split kernel on the dot form
-  if constexpr (true) {
-#else
-  if constexpr (DOT2) {
-#endif
-    typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
-    // the (-1, 0) / (0, -1) pairs as SGPR values: as a VOP2 inline constant "-1.0" the hardware does not read (-1, 0)
-    uint32_t c0_, c1_;
-    asm("s_mov_b32 %0, 0xbf80" : "=s"(c0_));  // (not volatile: hoisted out of the loops)
-    asm("s_mov_b32 %0, 0xbf800000" : "=s"(c1_));
-    const b2_ e0 = __builtin_bit_cast(b2_, c0_), e1 = __builtin_bit_cast(b2_, c1_);
-    auto res = [&](uint32_t p, float x0, float x1, float& y0, float& y1) __attribute__((always_inline)) {
-      const b2_ q = __builtin_bit_cast(b2_, p);
-      y0 = __builtin_amdgcn_fdot2_f32_bf16(q, e0, x0, false);
-      y1 = __builtin_amdgcn_fdot2_f32_bf16(q, e1, x1, false);
-    };
-    const uint32_t h0 = x6_pack(v.x, v.y), h1 = x6_pack(v.z, v.w);
-    float r0, r1, r2, r3, s0, s1, s2, s3;
-    res(h0, v.x, v.y, r0, r1);
-    res(h1, v.z, v.w, r2, r3);
-    const uint32_t m0 = x6_pack(r0, r1), m1 = x6_pack(r2, r3);
-    res(m0, r0, r1, s0, s1);
-    res(m1, r2, r3, s2, s3);
-    h = make_uint2(h0, h1);
-    m = make_uint2(m0, m1);
-    l = make_uint2(x6_pack(s0, s1), x6_pack(s2, s3));
-    return;
-  }
   const uint32_t h0 = x6_pack(v.x, v.y), h1 = x6_pack(v.z, v.w);
   const float r0 = v.x - nerf_bf16_lo(h0), r1 = v.y - nerf_bf16_hi(h0);
   const float r2 = v.z - nerf_bf16_lo(h1), r3 = v.w - nerf_bf16_hi(h1);
@@ -92,24 +49,12 @@ __device__ __forceinline__ void x6_split4(const float4 v, uint2& h, uint2& m, ui
 // chain on one accumulator (a dependent 32x32x16 MFMA waits for its predecessor's result).
 __device__ constexpr int X6_PA[6] = {2, 1, 0, 1, 0, 0};
 __device__ constexpr int X6_PB[6] = {0, 1, 2, 0, 1, 0};
-// the forward kernels' order: the same as X6_PA / X6_PB (lo.hi first).  A hi.lo-first order measured 0.635 -> 0.629 ms
-// per fine layer in round 3; with the LDS epilogue (round 4) its training run is slower (227.9k vs 229.3k rays/s) and
-// its 3000-step PSNR (25.93 dB, sd 0.30 over 3 jitter seeds, 8 views) sits inside the default's band (26.12 dB, sd
-// 0.16): decided by speed, lo.hi first is kept (profiles/r04/psnr_band.txt)
-#ifdef NERF_X6_FWD_HIFIRST  // A/B builds: the hi.lo-first forward order (PSNR noise-band study, round 4)
-__device__ constexpr int X6F_PA[6] = {0, 2, 1, 1, 0, 0};
-__device__ constexpr int X6F_PB[6] = {2, 0, 1, 0, 1, 0};
-#else
-__device__ constexpr int X6F_PA[6] = {2, 1, 0, 1, 0, 0};
-__device__ constexpr int X6F_PB[6] = {0, 1, 2, 0, 1, 0};
-#endif
+// The forward uses the same order.  A hi.lo-first forward order ran slower with the LDS epilogue (227.9k vs 229.3k
+// rays/s) and its 3000-step PSNR sat inside the default's band (profiles/r04/psnr_band.txt): lo.hi first is kept.
 // acc_[TM_][TN_] += over the six terms; MFMA(first_, second_) operands: NT passes (B fragment, A fragment) so the
 // accumulator is C^T (gemm_bf16.hpp); the weight gradient passes (G^T fragment, X fragment)
-#ifndef NERF_X6_TERMS  // ablation builds only (tools/build_exp.sh): fewer terms -> wrong results, MFMA cost probe
-#define NERF_X6_TERMS 6
-#endif
 #define X6_MFMA_BLOCK(acc_, TM_, TN_, FIRST_, SECOND_)                                                      \
-  _Pragma("unroll") for (int t_ = 6 - NERF_X6_TERMS; t_ < 6; ++t_)                                        \
+  _Pragma("unroll") for (int t_ = 0; t_ < 6; ++t_)                                                        \
     _Pragma("unroll") for (int a_ = 0; a_ < TM_; ++a_)                                                    \
       _Pragma("unroll") for (int b_ = 0; b_ < TN_; ++b_)                                                  \
         acc_[a_][b_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FIRST_, SECOND_, acc_[a_][b_], 0, 0, 0);
@@ -155,129 +100,6 @@ static __global__ void x6_planes_kernel(X6Jobs jobs) {
   }
 }
 
-// ------------------------------------------------------------------------------------------ gemm_nt_x6
-// 128 x 128 output tile per 256-thread workgroup (four 64 x 64 wave tiles of 2 x 2 MFMA tiles), BK = 32 (two MFMA
-// k-steps per slab).  The activation operand goes HBM -> registers in fragment layout (lane (r, h) of row block a:
-// row r, k = 8 h .. 8 h + 7 of each 16-k step = two float4) and is split there, so only the pre-split weight planes
-// pass through LDS: a first version that staged all six piece images through LDS ran at MFMA busy 0.31 with the LDS
-// pipe as busy as the matrix cores (12 ds_read_b128 + 9 ds_write per 24 MFMAs, PMC 4e7 bank-conflict cycles per
-// launch).  Weight planes: [3][128][40] bf16 per stage (80-B pitch: 16 consecutive rows hit 16 distinct 16-B bank
-// slots), double-buffered, 60 KiB per workgroup -> two workgroups per CU.  The activation loads of slab k + 2 are
-// issued as slab k's registers are consumed (two register sets); the weight slab k + 1 (L2-resident) is staged in
-// registers during slab k and written to LDS after it (one barrier per slab).
-// B: three planes of [N][ldb] bf16, plane stride bplane.  Requirements (host): M % 128 == 0, N % 128 == 0,
-// K % 32 == 0, lda % 4 == 0, ldb % 8 == 0.
-template <int EPI, int BK = 32, int MINW = 2>
-__global__ __launch_bounds__(256, MINW) void gemm_nt_x6_kernel(const float* __restrict__ A, int lda,
-                                                              const nerf_bf16* __restrict__ Bp, int ldb, int64_t bplane,
-                                                              const float* __restrict__ bias, float* __restrict__ C,
-                                                              int ldc, const uint32_t* __restrict__ mbits, int ldmb,
-                                                              uint32_t* __restrict__ mbits_out, int K, int n_ntiles) {
-  constexpr int BM = 128, BN = 128, WTM = 64, WTN = 64, TM = 2, TN = 2;
-  constexpr int KS = BK / 16;   // MFMA k-steps per slab
-  constexpr int CPR = BK / 8;   // 16-B weight chunks per row per slab
-  static_assert(BK == 16 || BK == 32, "slab");
-  constexpr int LS = BK + 8;    // 48 / 80-B pitch: 16 consecutive rows hit 16 distinct 16-B bank slots
-  constexpr int PL = BN * LS;  // one weight piece image
-  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[2 * 3 * PL];
-
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int mt = tile / n_ntiles, nt = tile - mt * n_ntiles;
-  const int64_t m0 = (int64_t)mt * BM;
-  const int n0 = nt * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 31, lh = lane >> 5;
-  const nerf_bf16* Bb = Bp + (int64_t)n0 * ldb;
-  // this lane's activation rows (uniform tile base + 32-bit lane offsets)
-  const float* At = A + (m0 + wm * WTM) * lda;
-  int aoff[TM];
-#pragma unroll
-  for (int a = 0; a < TM; ++a) aoff[a] = (a * 32 + li) * lda + 8 * lh;
-
-  // register sets: ra[set][a][ks] = the 8 fp32 of row block a, k-step ks (two float4)
-  float4 ra[2][TM][KS][2];
-  uint4 rb[3][KS];  // weight slab: 3 planes x 128 rows x CPR chunks of 16 B (thread: chunks t + 256 i)
-#define X6_ALOAD(set_, k0_)                                                                                \
-  _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                          \
-    _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                     \
-      _Pragma("unroll") for (int hf = 0; hf < 2; ++hf)                                                    \
-        ra[set_][a][ks][hf] = *reinterpret_cast<const float4*>(At + aoff[a] + (k0_) + 16 * ks + 4 * hf);
-#define X6_BLOAD(k0_)                                                                                      \
-  _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                           \
-    _Pragma("unroll") for (int i = 0; i < KS; ++i) {                                                      \
-      const int c = tid + 256 * i;                                                                        \
-      rb[p][i] = *reinterpret_cast<const uint4*>(Bb + p * bplane + (int64_t)(c / CPR) * ldb + (k0_) + 8 * (c % CPR)); \
-    }
-#define X6_BSTORE(buf_)                                                                                    \
-  _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                           \
-    _Pragma("unroll") for (int i = 0; i < KS; ++i) {                                                      \
-      const int c = tid + 256 * i;                                                                        \
-      *reinterpret_cast<uint4*>(smem + ((buf_) * 3 + p) * PL + (c / CPR) * LS + 8 * (c % CPR)) = rb[p][i]; \
-    }
-
-  nerf_f32x16 acc[TM][TN];
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  const int nk = K / BK;
-  X6_ALOAD(0, 0);
-  X6_ALOAD(1, (nk > 1 ? 1 : 0) * BK);
-  X6_BLOAD(0);
-  X6_BSTORE(0);
-  __syncthreads();
-  for (int kt0 = 0; kt0 < nk; kt0 += 2) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {  // slab kt = kt0 + j: LDS buffer j, activation register set j
-      const int kt = kt0 + j;
-      if (kt < nk) {
-        X6_BLOAD((kt + 1 < nk ? kt + 1 : kt) * BK);
-        const nerf_bf16* S = smem + j * 3 * PL;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          nerf_bf16x8 af[TM][3], bf[TN][3];
-#pragma unroll
-          for (int a = 0; a < TM; ++a) {
-            uint2 h0, m0_, l0, h1, m1, l1;
-            x6_split4(ra[j][a][ks][0], h0, m0_, l0);
-            x6_split4(ra[j][a][ks][1], h1, m1, l1);
-            af[a][0] = __builtin_bit_cast(nerf_bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-            af[a][1] = __builtin_bit_cast(nerf_bf16x8, make_uint4(m0_.x, m0_.y, m1.x, m1.y));
-            af[a][2] = __builtin_bit_cast(nerf_bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-          }
-#pragma unroll
-          for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-              bf[b][p] = *reinterpret_cast<const nerf_bf16x8*>(S + p * PL + (wn * WTN + b * 32 + li) * LS + 16 * ks +
-                                                               8 * lh);
-          X6_MFMA_BLOCK(acc, TM, TN, bf[b_][X6F_PB[t_]], af[a_][X6F_PA[t_]])  // the forward order (as gemm_nt_x6w)
-        }
-        // set j is consumed: slab kt + 2 streams into it while slab kt + 1 is computed
-        X6_ALOAD(j, (kt + 2 < nk ? kt + 2 : nk - 1) * BK);
-        X6_BSTORE(j ^ 1);
-        __syncthreads();
-      }
-    }
-  }
-#undef X6_ALOAD
-#undef X6_BLOAD
-#undef X6_BSTORE
-
-#ifdef NERF_X6_NOSTORE  // ablation builds only: the epilogue's cost (outputs left stale)
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b) asm volatile("" ::"v"(acc[a][b]));
-#else
-  ntb_epilogue<TM, TN, WTM, WTN, EPI, 0>(acc, m0 + wm * WTM, n0 + wn * WTN, li, lh, bias, C, ldc, mbits, ldmb,
-                                         mbits_out);
-#endif
-}
 
 // ------------------------------------------------------------------------------------------ LDS-staged epilogue
 // The C^T accumulator leaves lane (li, lh) with row li, columns 8q + 4lh .. + 3 of each 32 x 32 block: the direct
@@ -285,7 +107,8 @@ __global__ __launch_bounds__(256, MINW) void gemm_nt_x6_kernel(const float* __re
 // outputs leave at the store-issue rate while the matrix cores idle (cdna_hip_programming.md T21).  Here each block
 // goes registers -> a private [32][36] fp32 LDS tile (144-B pitch) -> registers as 8 lanes per row, so every store
 // instruction writes 8 whole 128-B lines.  Bias / ReLU / mask words are applied in registers first, exactly as
-// ntb_epilogue does (same fp32 operations, bitwise the same outputs).
+// ntb_epilogue does (same fp32 operations, bitwise the same outputs).  Against the direct stores
+// (profiles/r04/x6_epilogue_ab.txt): fwd 0.625 -> 0.591 ms, dgrad 0.669 -> 0.610 ms per fine layer.
 constexpr int X6E_PITCH = 36;
 constexpr int X6E_WAVE_FLOATS = 32 * X6E_PITCH;
 template <int TM, int TN, int EPI>
@@ -347,88 +170,41 @@ __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int6
   }
 }
 
-#ifdef NERF_X6W_STAMPS  // diagnostic builds only (tools/x6_stamps.py): s_memtime per pipeline point, one workgroup
-__device__ unsigned long long nerf_x6_stamps[2][8][128];
-#define X6W_STAMP()                                                                                       \
-  if (stamp_on) {                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                           \
-    if (lane == 0 && si_ < 128) nerf_x6_stamps[BIGSMALL ? 1 : 0][wave][si_] = t_;                          \
-    ++si_;                                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-  }
-#else
-#define X6W_STAMP()
-#endif
 // ------------------------------------------------------------------------------------------ gemm_nt_x6w
-// Wide-wave form of gemm_nt_x6: a (64 NW) x 128 workgroup tile whose NW waves each own 64 rows x ALL 128 columns
-// (2 x 4 MFMA tiles), so every activation row is loaded and split by exactly one wave (gemm_nt_x6's 64 x 64 waves
-// split each row twice) and the split VALU work per MFMA halves.  Weight planes [3][128][BK + 8] bf16
-// double-buffered in LDS; B fragments are read per pair of column blocks so that at most 24 VGPRs of them are live.
-// Requirements as gemm_nt_x6 with M % (32 TM NW) == 0 and K % BK == 0.  Default BK = 32, NW = 8 (512 x 128 tiles, one
-// workgroup per CU): C2 step 204.0k -> 207.5-209.0k rays/s over BK = 16, NW = 4 (fwd / dgrad 0.65 -> 0.63 ms).
-// TM = 1 (32-row waves; the BIGSMALL input gradients, whose 256 accumulator registers per 64-row wave allowed only one
-// wave per SIMD): 256 x 128 tiles at two waves per SIMD.
-#ifndef NERF_X6W_PAIRB
-#define NERF_X6W_PAIRB 0
-#endif
-#ifndef NERF_X6W_PAIRB3
-#define NERF_X6W_PAIRB3 0
-#endif
-constexpr bool defined_regb() {
-#ifdef NERF_X6W_REGB
-  return true;
-#else
-  return false;
-#endif
-}
-// TN_: 32-column blocks per wave (= the workgroup's columns / 32).  TN_ = 8 with TM = 1 (A/B builds,
-// NERF_X6_FWD_TN8): 256 x 256 tiles of 32 x 256 waves, so each activation row is split by ONE workgroup instead of one
-// per 128-column tile, at the same per-accumulator MFMA order (bitwise the same outputs).
-template <int EPI, int BK = 32, int NW = 8, bool BIGSMALL = false, int TM = 2, int MINW = (BIGSMALL ? 1 : 8 / NW),
-          int NKC = 0, int TN_ = 4>
-__global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float* __restrict__ A, int lda,
-                                                                     const nerf_bf16* __restrict__ Bp, int ldb,
-                                                                     int64_t bplane, const float* __restrict__ bias,
-                                                                     float* __restrict__ C, int ldc,
-                                                                     const uint32_t* __restrict__ mbits, int ldmb,
-                                                                     uint32_t* __restrict__ mbits_out, int K,
-                                                                     int n_ntiles) {
-  constexpr int NT = 64 * NW;                     // threads
-  constexpr int WTM = 32 * TM, BM = WTM * NW, TN = TN_, BN = 32 * TN_, WTN = BN;
-  constexpr int KS = BK / 16, CPR = BK / 8;       // MFMA k-steps / 16-B weight chunks per row, per slab
-  constexpr int BCH = 3 * BN * CPR / NT;          // weight chunks per thread per slab
-#ifdef NERF_X6W_REGB  // register staging: whole 16-B chunks per thread (the GLDS DMA groups are checked below)
-  static_assert((3 * BN * CPR) % NT == 0 && (BN * CPR) % NT == 0, "weight staging");
-#endif
-#if !defined(NERF_X6W_REGB) || defined(NERF_X6W_SWIZZLE)
-  // weight images [BN][BK] bf16 unpadded, 16-B chunk q of row r in slot q ^ ((r >> 2) & 3) (BK = 32: four chunks per
-  // 64-B row): the staging writes (4 rows x 4 chunks per 16-lane group) and the fragment reads (16 consecutive rows,
-  // one chunk) both hit 16 distinct 16-B bank slots.  The 80-B padded pitch it replaces was 2-way conflicted on the
-  // staging writes (PMC SQ_LDS_BANK_CONFLICT 8.5e6 cycles per fine forward launch, profiles/r04/pmc_split.txt).
+// 256 x (32 TN) output tile per 512-thread workgroup (one per CU): each of the eight waves owns 32 rows x ALL columns
+// of the tile, so every activation row is loaded and split by exactly one wave.  The activation operand goes HBM ->
+// registers in fragment layout (lane (r, h): row r, k = 8 h .. 8 h + 7 of each 16-k step = two float4) and is split
+// there, so only the pre-split weight planes pass through LDS (staging all six piece images through LDS left the LDS
+// pipe as busy as the matrix cores).  Slabs of BK = 32 (two MFMA k-steps); weight images [3][BN][32] bf16,
+// double-buffered; B fragments are read per pair of column blocks so that at most 24 VGPRs of them are live.
+// B: three planes of [N][ldb] bf16, plane stride bplane.  Requirements (host): M % 256 == 0, N % (32 TN) == 0,
+// K % 64 == 0 (the slabs are walked in pairs), lda % 4 == 0, ldb % 8 == 0.
+//   forward        <EPI_BIAS_RELU, false, 0, 8>: 256 x 256 tiles, each activation row split by ONE workgroup instead of
+//                  one per 128-column tile (profiles/r05/x6_variants_ab.txt: 0.572 -> 0.539 ms per fine layer)
+//   input gradient <EPI_MASK, true, 8, 4>: 256 x 128 tiles at two waves per SIMD, split accumulators (BIGSMALL below;
+//                  0.73-0.75 -> 0.665 ms per fine layer against 64-row waves at one per SIMD), K = 256 unrolled on
+//                  three activation register sets (NKC below)
+template <int EPI, bool BIGSMALL, int NKC, int TN>
+__global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __restrict__ A, int lda,
+                                                             const nerf_bf16* __restrict__ Bp, int ldb, int64_t bplane,
+                                                             const float* __restrict__ bias, float* __restrict__ C,
+                                                             int ldc, const uint32_t* __restrict__ mbits, int ldmb,
+                                                             uint32_t* __restrict__ mbits_out, int K, int n_ntiles) {
+  constexpr int BK = 32, NW = 8, TM = 1;          // slab depth, waves, 32-row blocks per wave
+  constexpr int WTM = 32 * TM, BM = WTM * NW, BN = 32 * TN;
+  constexpr int KS = BK / 16;                     // MFMA k-steps per slab
+  // weight images [BN][BK] bf16 unpadded, 16-B chunk q of row r in slot q ^ ((r >> 2) & 3) (four chunks per 64-B row):
+  // the staging writes (4 rows x 4 chunks per 16-lane group) and the fragment reads (16 consecutive rows, one chunk)
+  // both hit 16 distinct 16-B bank slots.  The 80-B padded pitch it replaces was 2-way conflicted on the staging
+  // writes (PMC SQ_LDS_BANK_CONFLICT 8.5e6 cycles per fine forward launch, profiles/r04/pmc_split.txt).
   constexpr int LS = BK;
   static_assert(BK == 32, "the swizzle assumes four 16-B chunks per row");
   auto sw = [](int r, int q) { return q ^ ((r >> 2) & 3); };
-#else  // A/B builds: the 80-B padded pitch
-  constexpr int LS = BK + 8;
-  auto sw = [](int r, int q) { return q; };
-#endif
   constexpr int PL = BN * LS;
-  // PB: one workgroup barrier per PAIR of slabs (four weight buffers: the next pair is DMA'd into the two the previous
-  // pair read, released by that pair's barrier) instead of one per slab — the waves arrive at a slab barrier skewed
-  // (s_memtime stamps, round 4: ~1.9k of a 9.55k-cycle forward slab), and a barrier every other slab pays that wait
-  // once per two slabs.  The two-set, non-A3 loop only.
-  constexpr bool PB = NERF_X6W_PAIRB && !(NKC > 0) && !defined_regb();
-  // the same for the three-set (A3) input-gradient loop: pairs of the fully unrolled slab sequence
-  constexpr bool PB3 = NERF_X6W_PAIRB3 && (NKC > 0) && !defined_regb();
-  constexpr int NBUF = (PB || PB3) ? 4 : 2;
-  // the epilogue tiles reuse the weight images (12-wave workgroups: a little more than the two buffers)
-  constexpr int SMEM_E = (NBUF * 3 * PL > NW * X6E_WAVE_FLOATS * 2) ? NBUF * 3 * PL : NW * X6E_WAVE_FLOATS * 2;
-  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[SMEM_E];
+  // the epilogue tiles reuse the two weight buffers
+  static_assert(2 * 3 * PL >= NW * X6E_WAVE_FLOATS * 2, "epilogue tiles");
+  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[2 * 3 * PL];
 
-#ifdef NERF_X6W_STAGGER  // probe builds: every other workgroup starts ~NERF_X6W_STAGGER x 64 clocks late
-  if ((blockIdx.x >> 3) & 1) __builtin_amdgcn_s_sleep(NERF_X6W_STAGGER);
-#endif
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = tile / n_ntiles, nt = tile - mt * n_ntiles;
   const int64_t m0 = (int64_t)mt * BM;
@@ -441,54 +217,36 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
 #pragma unroll
   for (int a = 0; a < TM; ++a) aoff[a] = (a * 32 + li) * lda + 8 * lh;
 
-#ifndef NERF_X6W_REGB  // NERF_X6W_REGB (A/B builds): register-staged weight slabs
-  constexpr bool GLDS = true;
-#else
-  constexpr bool GLDS = false;
-#endif
-  // NKC > 0 (K = NKC BK at compile time, TM = 1): three activation register sets, the slab loop fully unrolled — slab
-  // kt + 2's loads are issued at the start of slab kt, after its weight DMA, so the end-of-slab weight wait leaves them
-  // in flight (two slabs of latency instead of one)
+  // NKC > 0 (K = NKC BK at compile time): three activation register sets, the slab loop fully unrolled — slab kt + 2's
+  // loads are issued at the start of slab kt, after its weight DMA, so the end-of-slab weight wait leaves them in
+  // flight (two slabs of latency instead of one; profiles/r04/x6_a3_ab.txt: 0.597 -> 0.584 ms per fine launch)
   constexpr bool A3 = NKC > 0;
-  static_assert(!A3 || TM == 1, "three activation sets: 32-row waves");
   float4 ra[A3 ? 3 : 2][TM][KS][2];
-  const uint32_t bofs = (uint32_t)(((tid / CPR) * ldb + 8 * (tid % CPR)) * (int)sizeof(nerf_bf16));  // bytes
-  uint4 rb[GLDS ? 1 : BCH];
-  // GLDS: the weight slab DMA'd straight into the LDS image (global_load_lds_dwordx4, no VGPRs): one wave-instruction
+  // the weight slab is DMA'd straight into the LDS image (global_load_lds_dwordx4, no VGPRs): one wave-instruction
   // fills 16 rows x 64 B of a piece image, lane l -> row l / 4, slot l % 4, so the swizzle goes on the source: lane l
   // reads chunk (l % 4) ^ ((row >> 2) & 3) = (l & 3) ^ ((l >> 4) & 3) of its row.  Issued as inline asm after the touch
   // of the slab's activation registers (hipcc neither counts these loads nor drains them at its own waits).  Against
-  // register staging (profiles/r04/x6_glds_ab.txt, C2 on MI355X): fwd 0.595 -> 0.572-0.583 ms, dgrad 0.614 ->
-  // 0.588-0.594 ms per fine launch, 218.5k -> 221k rays/s, the same loss bits; s_memtime stamps of the forward: slab
-  // 11.4k -> 9.6k cycles, its "weight store + barrier" tail 3.5k -> 1.9k
+  // register staging (profiles/r04/x6_glds_ab.txt): fwd 0.595 -> 0.572-0.583 ms, dgrad 0.614 -> 0.588-0.594 ms per fine
+  // launch, the same loss bits
   constexpr int GPP = BN * BK * 2 / 1024, GPW = 3 * GPP / NW;  // 1-KiB groups per piece image / per wave
-  // GLDS: the NW waves' GPW groups each must cover the three piece images' 3 GPP 1-KiB groups exactly
-  static_assert(!GLDS || (BK == 32 && GPW * NW == 3 * GPP && GPP * 1024 == BN * BK * 2), "GLDS staging");
+  // the NW waves' GPW groups each must cover the three piece images' 3 GPP 1-KiB groups exactly
+  static_assert(GPW * NW == 3 * GPP && GPP * 1024 == BN * BK * 2, "weight staging");
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t gofs = (uint32_t)((((lane >> 2) * ldb) + 8 * ((lane & 3) ^ ((lane >> 4) & 3))) * 2);
-  const uint32_t smem_u32 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;  // chunk c = tid + NT i: plane c / (BN CPR), row (c / CPR) % BN, chunk c % CPR
+  const uint32_t smem_u32 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
 #define X6W_ALOAD(set_, k0_)                                                                              \
   _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                         \
     _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                    \
       _Pragma("unroll") for (int hf = 0; hf < 2; ++hf)                                                   \
         ra[set_][a][ks][hf] = *reinterpret_cast<const float4*>(At + aoff[a] + (k0_) + 16 * ks + 4 * hf);
-  // ASMB: the weight-slab loads as inline asm.  The compiler sinks plain loads to just before their LDS writes, which
-  // exposes an L2 round trip per slab; in the BIGSMALL input-gradient kernel that cost 0.78 -> 0.72 ms per fine layer
-  // (64-row waves, one per SIMD; measured on MI355X).  Issued after the wave's activation registers of the slab have landed
-  // (the touch below), so the compiler's counted waits on its own activation loads never wait on these as well.  At two
-  // waves per SIMD the extra live registers spill (fwd 0.62 -> 0.65 ms): plain loads there.  32-row waves (TM = 1) have
-  // the registers: a forward of that shape went 0.76 -> 0.655 ms with them, still behind 0.63 ms for 64-row waves.
-  constexpr bool ASMB = !GLDS && (BIGSMALL || TM == 1);
-  constexpr bool ASML = ASMB || GLDS;  // weight loads hipcc does not count
-  // B fragments are read per pair of column blocks (2 x 3 fragments live).  Measured and not kept (round 4,
-  // profiles/r04/x6_bfrag_ab.txt): one block at a time (fwd 0.603 -> 0.612 ms), with the next block read under the
-  // current block's MFMAs (0.613-0.619), and one block at a time with inline-asm weight loads (0.599-0.601).  Also not
-  // kept: the two 4-wave halves staggered by one barrier (ping-pong: one half's 24-MFMA cluster under the other's split
-  // and fragment reads, three DMA'd weight buffers, two barriers per cluster): fwd 0.58 -> 0.64, dgrad 0.59 -> 0.67 ms
-  // (profiles/r04/x6_pingpong_ab.txt)
+  // B fragments are read per pair of column blocks (2 x 3 fragments live).  Measured and not kept
+  // (profiles/r04/x6_bfrag_ab.txt): one block at a time (fwd 0.603 -> 0.612 ms), with the next block read under the
+  // current block's MFMAs (0.613-0.619); the two 4-wave halves staggered by one barrier (ping-pong): fwd 0.58 -> 0.64,
+  // dgrad 0.59 -> 0.67 ms (profiles/r04/x6_pingpong_ab.txt)
   constexpr int BPG = 2;
+  // slab k0_'s weight DMA into buffer dbuf_, after the touch of activation set j
 #define X6W_BLOAD(k0_, dbuf_)                                                                             \
-  if constexpr (GLDS) {                                                                                   \
+  {                                                                                                       \
     _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                       \
       _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                  \
         asm volatile("" ::"v"(__builtin_bit_cast(x6_f32x4, ra[j][a][ks][0])),                            \
@@ -501,45 +259,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t" \
                    "s_mov_b32 m0, %0" : "=&s"(keep_) : "v"(gofs), "s"(sb_), "s"(dst_) : "memory");       \
     }                                                                                                     \
-  } else if constexpr (ASMB) {                                                                            \
-    _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                       \
-      _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                  \
-        asm volatile("" ::"v"(__builtin_bit_cast(x6_f32x4, ra[j][a][ks][0])),                            \
-                     "v"(__builtin_bit_cast(x6_f32x4, ra[j][a][ks][1])) : "memory");                     \
-    _Pragma("unroll") for (int i = 0; i < BCH; ++i) {                                                    \
-      /* NT divides BN CPR: chunk c's plane and the row base of its NT-chunk group are uniform, so the     \
-         address is a uniform SGPR base plus one 32-bit lane offset (bofs) instead of a VGPR pair a chunk */ \
-      const int pu = (NT * i) / (BN * CPR), ru = ((NT * i) % (BN * CPR)) / CPR;                          \
-      const nerf_bf16* sb_ = Bb + pu * bplane + (int64_t)ru * ldb + (k0_);                              \
-      x6_f32x4 v_;                                                                                        \
-      asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(v_) : "v"(bofs), "s"(sb_) : "memory");       \
-      rb[i] = __builtin_bit_cast(uint4, v_);                                                              \
-    }                                                                                                     \
-  } else {                                                                                                \
-    _Pragma("unroll") for (int i = 0; i < BCH; ++i) {                                                    \
-      const int c = tid + NT * i, p = c / (BN * CPR), r = (c / CPR) % BN, q = c % CPR;                   \
-      rb[i] = *reinterpret_cast<const uint4*>(Bb + p * bplane + (int64_t)r * ldb + (k0_) + 8 * q);       \
-    }                                                                                                     \
   }
-#define X6W_BWAIT()                                                                                       \
-  if constexpr (GLDS) {                                                                                   \
-    if constexpr (TM * KS * 2 == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                    \
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                                \
-  } else if constexpr (ASMB) {                                                                            \
-    static_assert(TM * KS * 2 == 8 || TM * KS * 2 == 4, "vmcnt: the activation loads after the weight loads"); \
-    if constexpr (TM * KS * 2 == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                    \
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                                \
-    _Pragma("unroll") for (int i = 0; i < BCH; ++i) {                                                    \
-      x6_f32x4 v_ = __builtin_bit_cast(x6_f32x4, rb[i]);                                                  \
-      asm volatile("" : "+v"(v_));                                                                        \
-      rb[i] = __builtin_bit_cast(uint4, v_);                                                              \
-    }                                                                                                     \
-  }
-#define X6W_BSTORE(buf_)                                                                                  \
-  if constexpr (!GLDS) _Pragma("unroll") for (int i = 0; i < BCH; ++i) {                                 \
-    const int c = tid + NT * i, p = c / (BN * CPR), r = (c / CPR) % BN, q = c % CPR;                     \
-    *reinterpret_cast<uint4*>(smem + ((buf_) * 3 + p) * PL + r * LS + 8 * sw(r, q)) = rb[i];             \
-  }
+  // the weight DMA done: the four activation loads (TM KS 2) issued after it stay in flight
+  static_assert(TM * KS * 2 == 4, "vmcnt: the activation loads after the weight DMA");
+#define X6W_BWAIT() asm volatile("s_waitcnt vmcnt(4)" ::: "memory")
 
   // BIGSMALL: the five small piece products accumulate in their own registers (2^-8 of the hi.hi sum, so the bf16
   // MFMA's one-guard-bit accumulator update loses 2^8 less there) and hi.hi gets 1 update per k-step instead of 6
@@ -560,17 +283,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
   {
     const int j = 0;
     X6W_BLOAD(0, 0);
-    if constexpr (PB || PB3) {  // host: K % (2 BK) == 0, so slab 1 exists
-      X6W_BLOAD(BK, 1);
-    }
-    if constexpr (ASML) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  X6W_BSTORE(0);
   __syncthreads();
-#ifdef NERF_X6W_STAMPS
-  const bool stamp_on = blockIdx.x == 777 && (BIGSMALL || EPI == EPI_BIAS_RELU);
-  int si_ = 0;
-#endif
   // one slab's k-steps on activation register set rj and weight buffer S
   auto slab_mfma = [&](const float4 (&rj)[TM][KS][2], const nerf_bf16* S, auto&& after_split) __attribute__((always_inline)) {
 #pragma unroll
@@ -579,14 +294,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
 #pragma unroll
           for (int a = 0; a < TM; ++a) {
             uint2 h0, m0_, l0, h1, m1, l1;
-            x6_split4<NERF_X6_DOT2_FWD && !BIGSMALL>(rj[a][ks][0], h0, m0_, l0);
-            x6_split4<NERF_X6_DOT2_FWD && !BIGSMALL>(rj[a][ks][1], h1, m1, l1);
+            x6_split4(rj[a][ks][0], h0, m0_, l0);
+            x6_split4(rj[a][ks][1], h1, m1, l1);
             af[a][0] = __builtin_bit_cast(nerf_bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
             af[a][1] = __builtin_bit_cast(nerf_bf16x8, make_uint4(m0_.x, m0_.y, m1.x, m1.y));
             af[a][2] = __builtin_bit_cast(nerf_bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
           }
           if (ks == KS - 1) after_split();  // the slab's activation registers are all split
-          X6W_STAMP();
 #pragma unroll
           for (int bp = 0; bp < TN / BPG; ++bp) {  // groups of BPG column blocks: BPG x 3 B fragments live
             nerf_bf16x8 bf[BPG][3];
@@ -611,48 +325,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
                           bf[b][X6_PB[t]], af[a][X6_PA[t]], acc[a][BPG * bp + b], 0, 0, 0);
                   } else {
                     acc[a][BPG * bp + b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                        bf[b][X6F_PB[t]], af[a][X6F_PA[t]], acc[a][BPG * bp + b], 0, 0, 0);
+                        bf[b][X6_PB[t]], af[a][X6_PA[t]], acc[a][BPG * bp + b], 0, 0, 0);
                   }
                 }
           }
-          X6W_STAMP();
         }
   };
-  X6W_STAMP();
-  if constexpr (PB3) {
-    static_assert(NKC % 2 == 0, "slab pairs");
-    // pair (kt0, kt0 + 1) in buffers b0, b0 + 1: the next pair's DMAs and slab kt0 + 2's activations go out at the
-    // pair's start (after the touch of set kt0 % 3), slab kt0 + 3's after slab kt0 (into the set it freed); one
-    // barrier per pair, which the next pair's DMAs wait on (vmcnt(8): the 8 activation loads issued after them stay
-    // in flight); the last pair loads nothing and drains
-#pragma unroll
-    for (int p = 0; p < NKC / 2; ++p) {
-      const int kt0 = 2 * p, b0 = kt0 & 3;
-      const bool more = kt0 + 2 < NKC;  // compile time (unrolled)
-      {
-        const int j = kt0 % 3;
-        if (more) {
-          X6W_BLOAD((kt0 + 2) * BK, b0 ^ 2);
-          X6W_BLOAD((kt0 + 3) * BK, (b0 ^ 2) + 1);
-        }
-      }
-      if (more) X6W_ALOAD((kt0 + 2) % 3, (kt0 + 2) * BK);
-      asm volatile("" ::: "memory");
-      slab_mfma(ra[kt0 % 3], smem + b0 * 3 * PL, [] {});
-      if (more) X6W_ALOAD((kt0 + 3) % 3, (kt0 + 3) * BK);
-      asm volatile("" ::: "memory");
-      slab_mfma(ra[(kt0 + 1) % 3], smem + (b0 + 1) * 3 * PL, [] {});
-      if (more) {
-        if constexpr (TM * KS * 2 == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      X6W_STAMP();
-      __syncthreads();
-      X6W_STAMP();
-    }
-  } else if constexpr (A3) {
+  if constexpr (A3) {
 #pragma unroll
     for (int kt = 0; kt < NKC; ++kt) {
       const int j = kt % 3;
@@ -667,92 +346,46 @@ __global__ __launch_bounds__(64 * NW, MINW) void gemm_nt_x6w_kernel(const float*
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      X6W_STAMP();
       __syncthreads();
-      X6W_STAMP();
     }
-  } else if constexpr (PB) {
+  } else {
     for (int kt0 = 0; kt0 < nk; kt0 += 2) {
-      const int b0 = kt0 & 3;  // this pair's buffers b0, b0 + 1; the next pair's b0 ^ 2, (b0 ^ 2) + 1
-      {
-        const int j = 0;  // (the DMA's touch: set 0 feeds this pair's first slab)
-        // past the end the last pair is DMA'd again into buffers nobody reads (the drain below covers it)
-        X6W_BLOAD((kt0 + 2 < nk ? kt0 + 2 : nk - 2) * BK, b0 ^ 2);
-        X6W_BLOAD((kt0 + 3 < nk ? kt0 + 3 : nk - 1) * BK, (b0 ^ 2) + 1);
-      }
-      asm volatile("" ::: "memory");
-      slab_mfma(ra[0], smem + b0 * 3 * PL, [&]() __attribute__((always_inline)) {
-        X6W_ALOAD(0, (kt0 + 2 < nk ? kt0 + 2 : nk - 1) * BK);
-        asm volatile("" ::: "memory");
-      });
-      slab_mfma(ra[1], smem + (b0 + 1) * 3 * PL, [&]() __attribute__((always_inline)) {
-        X6W_ALOAD(1, (kt0 + 3 < nk ? kt0 + 3 : nk - 1) * BK);
-        asm volatile("" ::: "memory");
-      });
-      // the next pair's two DMAs done; the two activation sets issued after them stay in flight
-      if constexpr (TM * KS * 2 == 8) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      X6W_STAMP();
-      __syncthreads();
-      X6W_STAMP();
-    }
-  } else
-  for (int kt0 = 0; kt0 < nk; kt0 += 2) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {  // slab kt = kt0 + j: LDS buffer j, activation register set j
-      const int kt = kt0 + j;
-      // ASMB: nk is even (host: K % (2 BK) == 0), so no guard — every path into the loop header then has the same
-      // loads in flight and the compiler's counted wait there stays vmcnt(8) instead of draining to vmcnt(0)
-      if (ASML || kt < nk) {
+      for (int j = 0; j < 2; ++j) {  // slab kt = kt0 + j: LDS buffer j, activation register set j
+        // nk is even (host: K % (2 BK) == 0), so no guard — every path into the loop header then has the same loads in
+        // flight and the compiler's counted wait there stays vmcnt(8) instead of draining to vmcnt(0)
+        const int kt = kt0 + j;
         X6W_BLOAD((kt + 1 < nk ? kt + 1 : kt) * BK, j ^ 1);
-        const nerf_bf16* S = smem + j * 3 * PL;
-#ifndef NERF_X6W_LATE_A  // set j's next loads issued right after its last split, pinned before the last k-step's MFMAs
-        // (profiles/r04/x6_early_a_ab.txt: fwd 0.582 -> 0.578 ms, C2 +0.5 %; with register-staged weights the same move
-        // was slower, x6_early_ab.txt).  NERF_X6W_LATE_A (A/B builds): after the slab's MFMAs
-        slab_mfma(ra[j], S, [&] {
+        // set j's next loads issued right after its last split, pinned before the last k-step's MFMAs
+        // (profiles/r04/x6_early_a_ab.txt: fwd 0.582 -> 0.578 ms, C2 +0.5 %)
+        slab_mfma(ra[j], smem + j * 3 * PL, [&] {
           X6W_ALOAD(j, (kt + 2 < nk ? kt + 2 : nk - 1) * BK);
           asm volatile("" ::: "memory");
         });
-#else
-        slab_mfma(ra[j], S, [] {});
-        X6W_ALOAD(j, (kt + 2 < nk ? kt + 2 : nk - 1) * BK);  // set j consumed: slab kt + 2 streams into it
-#endif
         X6W_BWAIT();
-        X6W_STAMP();
-        X6W_BSTORE(j ^ 1);
         __syncthreads();
-        X6W_STAMP();
       }
     }
+    // the last slab re-issued slab nk - 1's weight DMA into buffer 0, which the epilogue tiles below reuse; the loop's
+    // counted vmcnt covered it only while the (dead) activation loads after it were still issued.  Drain every wave's
+    // DMA and meet before any wave writes its epilogue tile, independent of what hipcc keeps.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   }
 #undef X6W_ALOAD
 #undef X6W_BLOAD
 #undef X6W_BWAIT
-#undef X6W_BSTORE
 
-  if constexpr (GLDS && !A3) {
-    // the two-set loop's last slab re-issued slab nk - 1's weight DMA into buffer 0, which the epilogue tiles below
-    // reuse; the loop's counted vmcnt covered it only while the (dead) activation loads after it were still issued.
-    // Drain every wave's DMA and meet before any wave writes its epilogue tile, independent of what hipcc keeps.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
   if constexpr (BIGSMALL) {
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
       for (int b = 0; b < TN; ++b) acc[a][b] += accs[a][b];
   }
-#if defined(NERF_X6W_REGEPI)  // A/B builds: the direct row-per-lane stores (32 rows x 32 B per store instruction)
-  ntb_epilogue<TM, TN, WTM, WTN, EPI, 0>(acc, m0 + wave * WTM, n0, li, lh, bias, C, ldc, mbits, ldmb, mbits_out);
-#else
   // the loop's last barrier freed the weight images: every wave stages its 32 x 32 blocks through a private LDS
-  // tile and stores whole 128-B row lines (8 lanes per row).  C2 bench on MI355X (profiles/r04/x6_epilogue_ab.txt):
-  // fwd 0.625 -> 0.591 ms, dgrad 0.669 -> 0.610 ms per fine layer, 208.0k -> 217.0k rays/s, bitwise the same loss
+  // tile and stores whole 128-B row lines (8 lanes per row; x6_epilogue_lds)
   x6_epilogue_lds<TM, TN, EPI>(acc, m0 + wave * WTM, n0, lane, bias, C, ldc, mbits, ldmb, mbits_out,
                                reinterpret_cast<float*>(smem) + wave * X6E_WAVE_FLOATS);
-#endif
-  X6W_STAMP();
 }
 
 // ------------------------------------------------------------------------------------------ gemm_wgrad_x6
@@ -792,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_x6_kernel(const float* __re
   const int li = lane & 31, lh = lane >> 5;
   const bool do_bias = (Pb != nullptr) && kt == 0 && wk == 0;
 
-  constexpr int PF = 4;  // register sets in flight, as in gemm_nt_x6_kernel
+  constexpr int PF = 4;  // register sets in flight
   float4 rg[PF][G_PER], rx[PF][X_PER];
 #define WX6_GLOAD(set_, m_)                                                                                \
   {                                                                                                        \

@@ -16,7 +16,6 @@
 //   transposed trunk weights, and S split-M partial slabs of the packed gradient.
 #include "gemm.hpp"
 #include "gemm_x6.hpp"
-#include "gemm_x6s.hpp"
 #include "mlp_common.hpp"
 #include "mlp_tail.hpp"
 #include "mlp_fwd_tail.hpp"
@@ -186,184 +185,70 @@ __global__ void transpose_kernel(TJobs jobs) {
 #define NERF_NT16_MINW 3
 #endif
 
-// MINW = 4 waves per SIMD: the register budget (128 unified VGPR+AGPR per lane) that lets four 256-thread
-// workgroups share a CU; measured +9..12 % over the unconstrained allocation (tools/gemm_bench.hip).
-template <int BM, int BN, int WAVES_M, int EPI>
-int launch_nt(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
-              const uint32_t* mbits, uint32_t* mbits_out, int64_t M, int N, int K, hipStream_t st) {
-  if (M % BM || N % BN || K % 16) return NERF_E_ARG;
-  const int ntn = N / BN;
-  const int64_t nblk = (M / BM) * ntn;
-#ifndef NERF_GEMM32
-  if constexpr (BM == 128 && BN == 128 && WAVES_M == 2) {  // the trunk GEMMs: 16x16x4 form (gemm.hpp)
-    gemm_nt16_kernel<128, 128, 2, EPI, NERF_NT16_MINW><<<(unsigned)nblk, 256, 0, st>>>(A, lda, B, ldb, bias, C, ldc, mbits,
-                                                                                       N / 32, mbits_out, K, ntn);
-    return NERF_OK;
-  }
-#endif
-  gemm_nt_kernel<BM, BN, WAVES_M, EPI, (BN >= 128 ? 4 : 1)><<<(unsigned)nblk, 256, 0, st>>>(A, lda, B, ldb, bias, C, ldc, mbits,
-                                                                           N / 32, mbits_out, K, ntn);
-  return NERF_OK;
-}
-
-// dispatch on N for the trunk-like GEMMs.  mbits: ReLU bitmask [M][N/32] read by EPI_MASK; mbits_out:
-// bitmask written by EPI_BIAS_RELU (nullable).
+// The native-fp32 trunk GEMMs (N = 256): 128 x 128 tiles of the 16x16x4 form.  mbits: ReLU bitmask [M][N/32] read by
+// EPI_MASK; mbits_out: bitmask written by EPI_BIAS_RELU (nullable).
 template <int EPI>
 int nt(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc, const uint32_t* mbits,
        uint32_t* mbits_out, int64_t M, int N, int K, hipStream_t st) {
-  if (N == 256 || N == 128)
-    return launch_nt<128, 128, 2, EPI>(A, lda, B, ldb, bias, C, ldc, mbits, mbits_out, M, N, K, st);
-  if (N == 32) return launch_nt<256, 32, 4, EPI>(A, lda, B, ldb, bias, C, ldc, mbits, mbits_out, M, N, K, st);
-  return NERF_E_ARG;
+  if (M % 128 || N != 256 || K % 16) return NERF_E_ARG;
+  const int ntn = N / 128;
+  gemm_nt16_kernel<128, 128, 2, EPI, NERF_NT16_MINW><<<(unsigned)((M / 128) * ntn), 256, 0, st>>>(
+      A, lda, B, ldb, bias, C, ldc, mbits, N / 32, mbits_out, K, ntn);
+  return NERF_OK;
 }
 
+// native-fp32 trunk weight gradient, N = 256: 128 x 128 tiles over the first 256 input columns, and for K = 64
+// (trunk.0) and the K = 320 remainder of trunk.4 (its encoding columns) one 256 x 64 block
 int wgrad(const float* G, int ldg, const float* X, int ldx, int tensor_w, const WS& w, int N, int K, hipStream_t st) {
   const Layout& L = layout();
   float* P = w.partial + L.off[tensor_w];
   float* Pb = w.partial + L.off[tensor_w + 1];
   const int ldp = L.cols[tensor_w];
   const int64_t slab = L.total;
-  if (N % 32 || K % 32) return NERF_E_ARG;
-  // one 256 x 64 block (trunk.0 and the K = 320 remainder of trunk.4): four 64 x 64 tiles per split (1024
-  // workgroups) staging 32 rows per slab.  Measured on MI355X at the fine net's M (per launch): 256x64 tiles
-  // at 16 / 32 rows 398 / 358 us, 128x64 323 us, 128x32 309 us, 64x64 at 16 rows 272 us, this 252 us.
-  auto narrow = [&](const float* Xn, float* Pn, float* Pbn) {
-    gemm_wgrad_kernel<64, 64, 2, 32><<<4 * w.S, 256, 0, st>>>(G, ldg, Xn, ldx, Pn, ldp, Pbn, slab, w.rps, w.Mp, 1, 4);
+  if (N != 256) return NERF_E_ARG;
+  auto t128 = [&](const float* Xk, float* Pk, float* Pbk) {
+    gemm_wgrad_kernel<128, 128, 2><<<4 * w.S, 256, 0, st>>>(G, ldg, Xk, ldx, Pk, ldp, Pbk, slab, w.rps, w.Mp, 2, 4);
   };
-  if (N == 256 && K == 64) {  // trunk.0
-    narrow(X, P, Pb);
-    return NERF_OK;
-  }
-  if (N >= 128 && K > 128 && K % 128 == 64) {  // trunk.4 (K = 320): 128x128 tiles + one 256x64 block
-    if (N != 256) return NERF_E_ARG;
-    const int kb = K - 64;
-    const int e = wgrad(G, ldg, X, ldx, tensor_w, w, N, kb, st);
-    if (e != NERF_OK) return e;
-    narrow(X + kb, P + kb, nullptr);
-    return NERF_OK;
-  }
-  if (N >= 128 && K % 128 == 0) {
-    const int nt = (N / 128) * (K / 128);
-    gemm_wgrad_kernel<128, 128, 2><<<nt * w.S, 256, 0, st>>>(G, ldg, X, ldx, P, ldp, Pb, slab, w.rps, w.Mp, K / 128, nt);
-  } else if (N >= 128 && K % 64 == 0) {
-    const int nt = (N / 128) * (K / 64);
-    gemm_wgrad_kernel<128, 64, 2><<<nt * w.S, 256, 0, st>>>(G, ldg, X, ldx, P, ldp, Pb, slab, w.rps, w.Mp, K / 64, nt);
-  } else if (N == 32 && K % 128 == 0) {
-    const int nt = K / 128;
-    gemm_wgrad_kernel<32, 128, 1, 64><<<nt * w.S, 256, 0, st>>>(G, ldg, X, ldx, P, ldp, Pb, slab, w.rps, w.Mp, K / 128, nt);
+  // the 256 x 64 block: four 64 x 64 tiles per split (1024 workgroups) staging 32 rows per slab.  Measured on MI355X
+  // at the fine net's M (per launch): 256x64 tiles at 16 / 32 rows 398 / 358 us, 128x64 323 us, 128x32 309 us, 64x64
+  // at 16 rows 272 us, this 252 us.
+  auto t64 = [&](const float* Xk, float* Pk, float* Pbk) {
+    gemm_wgrad_kernel<64, 64, 2, 32><<<4 * w.S, 256, 0, st>>>(G, ldg, Xk, ldx, Pk, ldp, Pbk, slab, w.rps, w.Mp, 1, 4);
+  };
+  if (K == 64) {
+    t64(X, P, Pb);
+  } else if (K == 256) {
+    t128(X, P, Pb);
+  } else if (K == 320) {
+    t128(X, P, Pb);
+    t64(X + 256, P + 256, nullptr);
   } else {
     return NERF_E_ARG;
   }
   return NERF_OK;
 }
 
-// split-product (bf16 x 6) forms of the trunk GEMMs (gemm_x6.hpp)
+// split-product (bf16 x 6) forms of the trunk GEMMs (gemm_x6.hpp), N = 256, M a multiple of 256 (the workspace pads
+// it): the forward (K = 64, 256 or 320) on 256 x 256 tiles, the input gradient (K = 256) on 256 x 128 tiles
 template <int EPI>
 int nt_x6(const float* A, int lda, const nerf_bf16* Bp, int ldb, int64_t bplane, const float* bias, float* C, int ldc,
           const uint32_t* mbits, uint32_t* mbits_out, int64_t M, int N, int K, hipStream_t st) {
-  if (M % 128 || N % 128 || K % 32 || lda % 4 || ldb % 8) return NERF_E_ARG;
-  const int ntn = N / 128;
-#ifndef NERF_X6_SQUARE  // (64 NW) x 128 tiles of 64 x 128 waves (gemm_nt_x6w); NERF_X6_SQUARE: 128 x 128 (A/B builds)
-#ifndef NERF_X6W_BK
-#define NERF_X6W_BK 32
-#endif
-#ifndef NERF_X6W_NW
-#define NERF_X6W_NW 8
-#endif
+  static_assert(EPI == EPI_BIAS_RELU || EPI == EPI_MASK, "trunk forward or input gradient");
+  if (M % 256 || N != 256 || lda % 4 || ldb % 8) return NERF_E_ARG;
   if constexpr (EPI == EPI_MASK) {
-    // input gradients: split accumulators (gemm_x6.hpp BIGSMALL) on 32-row waves, two per SIMD (256 x 128 tiles of 8
-    // waves): 0.73-0.75 -> 0.665 ms per fine layer against 64-row waves at one per SIMD, bitwise the same results
-#ifndef NERF_X6_DG_NW  // A/B builds: waves per input-gradient workgroup (4: two workgroups per CU)
-#define NERF_X6_DG_NW 8
-#endif
-    constexpr int DGM = 32 * NERF_X6_DG_NW;
-#ifdef NERF_X6_DG_SHARED  // A/B builds: 128 x 256 tiles, each activation slab split once and shared (gemm_x6s.hpp)
-    if (M % 128 == 0 && K == 256 && N == 256 && EPI == EPI_MASK) {
-      gemm_nt_x6s_kernel<EPI, 8><<<(unsigned)(M / 128), 512, 0, st>>>(A, lda, Bp, ldb, bplane, C, ldc, mbits, N / 32);
-      return NERF_OK;
-    }
-#endif
-#ifdef NERF_X6_DG_TN8  // A/B builds: input gradient on 128 x 256 tiles of 32 x 256 waves, one wave per SIMD (both
-    // accumulator sets, 256 registers, need the whole register file): each row split once instead of twice
-    if (M % 128 == 0 && K == 256 && N % 256 == 0) {
-      gemm_nt_x6w_kernel<EPI, 32, 4, true, 1, 1, 8, 8><<<(unsigned)((M / 128) * (N / 256)), 256, 0, st>>>(
-          A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, N / 256);
-      return NERF_OK;
-    }
-#endif
-#ifndef NERF_X6W_NOA3  // three activation register sets, K = 256 unrolled (NERF_X6W_NOA3: the two-set loop, A/B builds)
-    // (profiles/r04/x6_a3_ab.txt: 0.597 -> 0.584 ms per fine launch, C2 +0.5 %, bitwise the same)
-    if (M % DGM == 0 && K == 256) {
-      gemm_nt_x6w_kernel<EPI, 32, NERF_X6_DG_NW, true, 1, 8 / NERF_X6_DG_NW, 8><<<(unsigned)((M / DGM) * ntn),
-                                                                                64 * NERF_X6_DG_NW, 0, st>>>(
-          A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, ntn);
-      return NERF_OK;
-    }
-#endif
-    if (M % DGM == 0 && K % 64 == 0) {  // gemm_nt_x6w walks the slabs in pairs
-      gemm_nt_x6w_kernel<EPI, 32, NERF_X6_DG_NW, true, 1, 8 / NERF_X6_DG_NW><<<(unsigned)((M / DGM) * ntn),
-                                                                             64 * NERF_X6_DG_NW, 0, st>>>(
-          A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, ntn);
-      return NERF_OK;
-    }
+    if (K != 256) return NERF_E_ARG;
+    gemm_nt_x6w_kernel<EPI, true, 8, 4><<<(unsigned)((M / 256) * 2), 512, 0, st>>>(A, lda, Bp, ldb, bplane, bias, C, ldc,
+                                                                                   mbits, N / 32, mbits_out, K, 2);
+  } else {
+    if (K % 64) return NERF_E_ARG;
+    gemm_nt_x6w_kernel<EPI, false, 0, 8><<<(unsigned)(M / 256), 512, 0, st>>>(A, lda, Bp, ldb, bplane, bias, C, ldc,
+                                                                              mbits, N / 32, mbits_out, K, 1);
   }
-#ifndef NERF_X6_K64_NW  // trunk.0 (K = 64: two slabs, the tile's 256 KiB of stores dominate): waves per workgroup
-#define NERF_X6_K64_NW 8
-#endif
-  if constexpr (NERF_X6_K64_NW != NERF_X6W_NW) {
-    if (K == 64 && EPI == EPI_BIAS_RELU && M % (64 * NERF_X6_K64_NW) == 0) {
-      gemm_nt_x6w_kernel<EPI, NERF_X6W_BK, NERF_X6_K64_NW><<<(unsigned)((M / (64 * NERF_X6_K64_NW)) * ntn),
-                                                             64 * NERF_X6_K64_NW, 0, st>>>(
-          A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, ntn);
-      return NERF_OK;
-    }
-  }
-#ifndef NERF_X6_FWD_TN8  // forward on 256 x 256 tiles of 32 x 256 waves: each activation row is split by one workgroup
-// instead of two (one per 128-column tile), at the same per-accumulator MFMA order — bitwise the same outputs.  C2 on
-// one box (profiles/r05/x6_variants_ab.txt): fwd 0.572 -> 0.539 ms per fine layer, 228.6k -> 233.0k rays/s.
-// NERF_X6_FWD_TN8=0 (A/B builds): the 512 x 128 tiles of 64 x 128 waves.
-#define NERF_X6_FWD_TN8 1
-#endif
-#if NERF_X6_FWD_TN8
-#ifdef NERF_X6_FWD_A3  // A/B builds: the K = 256 forward layers on three activation register sets (the A3 loop)
-  if (EPI == EPI_BIAS_RELU && N % 256 == 0 && M % 256 == 0 && K == 256) {
-    gemm_nt_x6w_kernel<EPI, 32, 8, false, 1, 1, 8, 8><<<(unsigned)((M / 256) * (N / 256)), 512, 0, st>>>(
-        A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, N / 256);
-    return NERF_OK;
-  }
-#endif
-  if (EPI == EPI_BIAS_RELU && N % 256 == 0 && M % 256 == 0 && K % 64 == 0) {
-    gemm_nt_x6w_kernel<EPI, 32, 8, false, 1, 1, 0, 8><<<(unsigned)((M / 256) * (N / 256)), 512, 0, st>>>(
-        A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, N / 256);
-    return NERF_OK;
-  }
-#endif
-#ifdef NERF_X6_FWD_W12  // A/B builds: forward on 32-row waves, NERF_X6_FWD_W12 (12 or 16) per workgroup (3 / 4 per SIMD)
-  if (EPI == EPI_BIAS_RELU && M % (32 * NERF_X6_FWD_W12) == 0 && K % 64 == 0) {
-    gemm_nt_x6w_kernel<EPI, 32, NERF_X6_FWD_W12, false, 1, 1><<<(unsigned)((M / (32 * NERF_X6_FWD_W12)) * ntn),
-                                                                64 * NERF_X6_FWD_W12, 0, st>>>(
-        A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32, mbits_out, K, ntn);
-    return NERF_OK;
-  }
-#endif
-  if (M % (64 * NERF_X6W_NW) == 0 && K % (2 * NERF_X6W_BK) == 0) {
-    gemm_nt_x6w_kernel<EPI, NERF_X6W_BK, NERF_X6W_NW><<<(unsigned)((M / (64 * NERF_X6W_NW)) * ntn), 64 * NERF_X6W_NW, 0,
-                                                        st>>>(A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, N / 32,
-                                                              mbits_out, K, ntn);
-    return NERF_OK;
-  }
-#endif
-#ifndef NERF_X6_NT_BK  // ablation / tuning builds: slab depth and workgroups per CU of the split NT GEMM
-#define NERF_X6_NT_BK 32
-#define NERF_X6_NT_MINW 2
-#endif
-  gemm_nt_x6_kernel<EPI, NERF_X6_NT_BK, NERF_X6_NT_MINW><<<(unsigned)((M / 128) * ntn), 256, 0, st>>>(A, lda, Bp, ldb, bplane, bias, C, ldc, mbits,
-                                                                      N / 32, mbits_out, K, ntn);
   return NERF_OK;
 }
 
-// trunk weight gradient, N = 256: 128 x 128 tiles over the first 256 input columns, 128 x 64 tiles over K = 64
-// (trunk.0) and the K = 320 remainder of trunk.4 (its encoding columns)
+// split trunk weight gradient, N = 256: one 512-thread workgroup per split over the first 256 input columns
+// (gemm_wgrad_x6w), 128 x 64 tiles over K = 64 (trunk.0) and the K = 320 remainder of trunk.4 (its encoding columns)
 int wgrad_x6(const float* G, int ldg, const float* X, int ldx, int tensor_w, const WS& w, int N, int K, hipStream_t st) {
   const Layout& L = layout();
   float* P = w.partial + L.off[tensor_w];
@@ -372,11 +257,7 @@ int wgrad_x6(const float* G, int ldg, const float* X, int ldx, int tensor_w, con
   const int64_t slab = L.total;
   if (N != 256 || ldg % 4 || ldx % 4) return NERF_E_ARG;
   auto t128 = [&](const float* Xk, float* Pk, float* Pbk) {
-#ifndef NERF_X6_WGRAD_TILES  // one 512-thread workgroup per split (gemm_wgrad_x6w); the A/B form: 4 x 128x128 tiles
     gemm_wgrad_x6w_kernel<<<w.S, 512, 0, st>>>(G, ldg, Xk, ldx, Pk, ldp, Pbk, slab, w.rps, w.Mp);
-#else
-    gemm_wgrad_x6_kernel<128, 128, 2><<<4 * w.S, 256, 0, st>>>(G, ldg, Xk, ldx, Pk, ldp, Pbk, slab, w.rps, w.Mp, 2, 4);
-#endif
   };
   auto t64 = [&](const float* Xk, float* Pk, float* Pbk) {
     // (a one-workgroup-per-split form reading G and X once, as gemm_wgrad_x6w, measured 185 -> 191 us per launch:
@@ -472,15 +353,6 @@ extern "C" int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, floa
   return nerf_launch_status();
 }
 
-#ifdef NERF_X6W_STAMPS  // diagnostic builds only: the split NT kernels' pipeline stamps (tools/x6_stamps.py)
-extern "C" int nerf_debug_x6_stamps(unsigned long long* out, int clear) {
-  if (clear) {
-    static unsigned long long zero[2 * 8 * 128] = {};
-    return nerf_hip_status(hipMemcpyToSymbol(HIP_SYMBOL(nerf_x6_stamps), zero, sizeof(zero)));
-  }
-  return nerf_hip_status(hipMemcpyFromSymbol(out, HIP_SYMBOL(nerf_x6_stamps), sizeof(nerf_x6_stamps)));
-}
-#endif
 
 extern "C" int nerf_mlp_fwd(const float* w, const float* x_d, int64_t M, float* rgb_sigma, void* ws, int64_t ws_bytes,
                             int training, hipEvent_t* ev, hipStream_t st) {

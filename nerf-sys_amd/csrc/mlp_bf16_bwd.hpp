@@ -216,23 +216,14 @@ __device__ __forceinline__ void bwd_compute(const LayerArgs& A, char* lds, int s
                      "+v"(gf[cb][3])::"memory");
       }
       SCHED_FENCE();
-#ifdef NERF_EXP_BWD_NOWG
-      asm volatile("" ::"v"(gf[cb][0]), "v"(gf[cb][1]), "v"(gf[cb][2]), "v"(gf[cb][3]), "v"(xf[cb]));
-#else
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] = h16_mfma(gf[cb][j], xf[cb], acc[j]);
-#endif
       SCHED_FENCE();
     });
     // ---- input gradient: dX^T[32 kb..][rows 32 mh..] over n in 16 k-steps
     nerf_f32x16 dacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) dacc[r] = 0.f;
-#ifdef NERF_EXP_BWD_XMFMA
-    nerf_f32x16 dacc2;  // probe of the odd-layer recompute's MFMA work: one more 16-step chain per tile (no LDS reads)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dacc2[r] = 0.f;
-#endif
     nerf_bf16x8 xm[2];
     static_for<0, 16>([&](auto KS) {
       constexpr int ks = decltype(KS)::value;
@@ -251,19 +242,9 @@ __device__ __forceinline__ void bwd_compute(const LayerArgs& A, char* lds, int s
         asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(wf), "+v"(g)::"memory");
       }
       SCHED_FENCE();
-#ifdef NERF_EXP_BWD_NODG
-      asm volatile("" ::"v"(wf), "v"(g));
-#else
       dacc = h16_mfma(wf, g, dacc);
-#endif
-#ifdef NERF_EXP_BWD_XMFMA
-      dacc2 = h16_mfma(g, wf, dacc2);
-#endif
       SCHED_FENCE();
     });
-#ifdef NERF_EXP_BWD_XMFMA
-    if (dacc2[0] == 1.2345e-30f) dacc[0] += 1.f;  // keeps the probe chain live
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xm[0]), "+v"(xm[1])::"memory");
     // ---- epilogue: lane li owns row 32 mh + li, register 4 q + e = column 8 q + 4 lh + e of the wave's block
     nerf_bf16* Dt = A.D + (r0 + (int64_t)t * TR + 32 * mh + li) * 256 + 32 * kb + 8 * lh;
@@ -281,13 +262,7 @@ __device__ __forceinline__ void bwd_compute(const LayerArgs& A, char* lds, int s
       // this lane now holds columns 16 pr + 8 lh .. + 7 of the block
       const uint4 xv = __builtin_bit_cast(uint4, xm[pr]);
       const uint4 o = make_uint4(relu_mask2(x.x, xv.x), relu_mask2(x.y, xv.y), relu_mask2(y.x, xv.z), relu_mask2(y.y, xv.w));
-#if defined(NERF_EXP_BWD_NOSTORE)
-      asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-#elif defined(NERF_EXP_BWD_NT)
-      __builtin_nontemporal_store(io_u32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<io_u32x4*>(Dt + 16 * pr));
-#else
       *reinterpret_cast<uint4*>(Dt + 16 * pr) = o;
-#endif
     }
     SCHED_FENCE();
   }
@@ -390,55 +365,16 @@ __device__ __forceinline__ void bias_acc(const IoSet& R, float (&bs)[8]) {
 __device__ __forceinline__ void io_step(IoSet& R, const LayerArgs& A, char* lds, int h, int j, int t, int nT,
                                         int64_t r0, int lane, float (&bs)[8]) {
   raw_barrier();  // T_t: tile t in stage t % 2 is complete; every wave is done with tile t - 1
-#ifndef NERF_EXP_BWD_NOIO
   if (h == 0 && t + 1 < nT) bias_acc(R, bs);
   io_store(R, lds + ((t + 1) % NSTG) * STB, j, lane);
   const int tl = t + 3 < nT ? t + 3 : nT - 1;
   io_load(R, A, r0 + (int64_t)tl * TR, h, j, lane);
-#endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // tile t + 1's LDS writes are done before T_{t+1}
-}
-
-#ifndef NERF_BWD_IOSETS
-#define NERF_BWD_IOSETS 2
-#endif
-// NERF_BWD_IOSETS == 3: three register sets, tile k in set k % 3; step t stores tile t + 1 and reloads its set with
-// tile t + 4 (three tiles in flight while tile t is computed)
-__device__ __forceinline__ void io_step3(IoSet& R, const LayerArgs& A, char* lds, int h, int j, int t, int nT,
-                                         int64_t r0, int lane, float (&bs)[8]) {
-  raw_barrier();
-  if (h == 0 && t + 1 < nT) bias_acc(R, bs);
-  io_store(R, lds + ((t + 1) % NSTG) * STB, j, lane);
-  const int tl = t + 4 < nT ? t + 4 : nT - 1;
-  io_load(R, A, r0 + (int64_t)tl * TR, h, j, lane);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
 __device__ __forceinline__ void bwd_io(const LayerArgs& A, char* lds, int h, int j, int nT, int64_t r0, int lane,
                                        float (&bs)[8]) {
   if (nT == 0) return;
-#if NERF_BWD_IOSETS == 3
-  {
-    IoSet R0, R1, R2;
-    io_load(R0, A, r0, h, j, lane);
-    io_load(R1, A, r0 + (int64_t)(nT > 1 ? 1 : nT - 1) * TR, h, j, lane);
-    io_load(R2, A, r0 + (int64_t)(nT > 2 ? 2 : nT - 1) * TR, h, j, lane);
-    if (h == 0) bias_acc(R0, bs);
-    io_store(R0, lds, j, lane);
-    io_load(R0, A, r0 + (int64_t)(nT > 3 ? 3 : nT - 1) * TR, h, j, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    int t = 0;
-    for (; t + 2 < nT; t += 3) {
-      io_step3(R1, A, lds, h, j, t, nT, r0, lane, bs);
-      io_step3(R2, A, lds, h, j, t + 1, nT, r0, lane, bs);
-      io_step3(R0, A, lds, h, j, t + 2, nT, r0, lane, bs);
-    }
-    if (t < nT) io_step3(R1, A, lds, h, j, t, nT, r0, lane, bs);
-    if (t + 1 < nT) io_step3(R2, A, lds, h, j, t + 1, nT, r0, lane, bs);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return;
-  }
-#endif
   IoSet R0, R1;
   io_load(R0, A, r0, h, j, lane);
   io_load(R1, A, r0 + (int64_t)(nT > 1 ? 1 : 0) * TR, h, j, lane);

@@ -190,97 +190,61 @@ __device__ __forceinline__ float acc_out(const nerf_f32x16& acc, int r, const fl
   return acc[r];
 }
 
-// k-step order of a stage (position p -> k-step kk), so that a wave starts on the columns IT wrote in the previous
-// epilogue and the barrier that publishes everyone else's columns overlaps those MFMAs:
-//   K_ID    identity (inputs already published: trunk.0 / colour 0 read E)
-//   K_ROT16 (p + 4 w) & 15        a 256-wide H input: wave w wrote columns 64w..64w+63 = k-steps 4w..4w+3
-//   K_L4    trunk.4 (K = 320): the own 4 h k-steps, the 4 enc k-steps (E, k-steps 16..19), the other 12 h k-steps
-//   K_ROT8  (p + 2 w) & 7         colour out over C0: wave w wrote columns 32w..32w+31 = k-steps 2w, 2w+1
-#ifndef NERF_FUSED_ROT
-#define NERF_FUSED_ROT 0
-#endif
-enum { K_ID = 0, K_ROT16 = 1, K_L4 = 2, K_ROT8 = 3 };
-template <int KIND>
-__device__ __forceinline__ int kpos(int p, int w) {
-  if (!NERF_FUSED_ROT) return p;
-  if (KIND == K_ROT16) return (p + 4 * w) & 15;
-  if (KIND == K_L4) return p < 4 ? 4 * w + p : (p < 8 ? 12 + p : ((4 * w + p - 4) & 15));
-  if (KIND == K_ROT8) return (p + 2 * w) & 7;
-  return p;
-}
-// A operand source of position p: 0 = H (k-step kk of the Hs tile), 1 = E (k-step kk - EOFF of the Es tile)
-template <int KIND, int ESRC>
-__device__ __forceinline__ constexpr bool from_e(int p) {
-  return ESRC == 1 || (KIND == K_L4 && (NERF_FUSED_ROT ? (p >= 4 && p < 8) : p >= 16));
-}
-// position of the in-stage barrier: after the wave's own k-steps with rotation, before position 0 without
-template <int BARROT>
-__device__ __forceinline__ constexpr int barpos() { return BARROT < 0 ? -1 : (NERF_FUSED_ROT ? BARROT : 0); }
+// A operand source of a stage: k-step p of the Hs tile, k-step p of the Es tile, or trunk.4 (K = 320): the 16 h
+// k-steps from Hs, then the 4 enc k-steps from Es
+enum { SRC_H = 0, SRC_E = 1, SRC_L4 = 2 };
 
-// One stage of the pipeline: KS positions over the fragments of tensor `wcur` (NBW fragment columns per wave from nb0)
-// in KIND order; A operands from LDS (TA 32-row blocks, rows ar0 + 32 a + li).  The ring holds positions 0..3 on
-// entry; consuming position p refills its slot with position p + 4 of this stage or, past the end, with position
-// p + 4 - KS of the NEXT stage (KSN positions in KINDN order, NBWN columns from nbn0 of tensor wnext).  BAR >= 0:
-// the workgroup barrier that publishes the other waves' epilogue sits between positions BAR - 1 and BAR.
-template <int KS, int NBW, int TA, int KIND, int ESRC, int BARROT, int KSN, int NBWN, int KINDN>
+// One stage of the pipeline: KS k-steps over the fragments of tensor `wcur` (NBW fragment columns per wave from nb0);
+// A operands from LDS (TA 32-row blocks, rows ar0 + 32 a + li).  The ring holds k-steps 0..3 on entry; consuming
+// k-step p refills its slot with k-step p + 4 of this stage or, past the end, with k-step p + 4 - KS of the NEXT stage
+// (KSN k-steps, NBWN columns from nbn0 of tensor wnext).  BAR: the workgroup barrier that publishes the other waves'
+// epilogue sits before k-step 0 (inputs already published, trunk.0 / colour 0 reading E: no barrier).
+template <int KS, int NBW, int TA, int SRC, bool BAR, int KSN, int NBWN>
 __device__ __forceinline__ void stage(nerf_f32x16 (&acc)[4][2], Ring& ring, __amdgpu_buffer_rsrc_t rs, int wcur,
                                       int nb0, int wnext, int nbn0, const nerf_bf16* Hs, const nerf_bf16* Es,
-                                      int pitch_h, int pitch_e, int ar0, int li, int lh, int lane, int w) {
+                                      int pitch_h, int pitch_e, int ar0, int li, int lh, int lane) {
   static_assert(KS % 4 == 0 && KSN % 4 == 0, "ring slot alignment across stages");
-  constexpr int EOFF = (KIND == K_L4) ? 16 : 0;
-  constexpr int BAR = barpos<BARROT>();
+  constexpr int EOFF = (SRC == SRC_L4) ? 16 : 0;
   auto afrag = [&](int p, int a) {
     const int r = ar0 + 32 * a + li;
-    const int kk = kpos<KIND>(p, w);
-    return from_e<KIND, ESRC>(p) ? lds_frag(Es + r * pitch_e + 16 * (kk - EOFF) + 8 * lh)
-                                 : lds_frag(Hs + r * pitch_h + 16 * kk + 8 * lh);
+    return (SRC == SRC_E || (SRC == SRC_L4 && p >= 16)) ? lds_frag(Es + r * pitch_e + 16 * (p - EOFF) + 8 * lh)
+                                                        : lds_frag(Hs + r * pitch_h + 16 * p + 8 * lh);
   };
   nerf_bf16x8 af[TA];
-  if (BAR != 0) {
+  if (!BAR) {
 #pragma unroll
     for (int a = 0; a < TA; ++a) af[a] = afrag(0, a);
   }
 #pragma unroll
   for (int p = 0; p < KS; ++p) {
-    if (p == BAR) {  // everyone's previous epilogue is in LDS past this point
+    // everyone's previous epilogue is in LDS past this point.  (Written inside the unrolled loop: with the barrier
+    // hoisted in front of it hipcc allocates differently and spills, 12-144 B of scratch per lane.)
+    if (BAR && p == 0) {
       bar();
 #pragma unroll
       for (int a = 0; a < TA; ++a) af[a] = afrag(p, a);
     }
-    nerf_bf16x8 an[TA];  // A fragments of the next position, read under this position's MFMAs
-    if (p + 1 < KS && p + 1 != BAR) {
+    nerf_bf16x8 an[TA];  // A fragments of the next k-step, read under this k-step's MFMAs
+    if (p + 1 < KS) {
 #pragma unroll
       for (int a = 0; a < TA; ++a) an[a] = afrag(p + 1, a);
     }
     nerf_bf16x8 bf[NBW];
 #pragma unroll
     for (int b = 0; b < NBW; ++b) bf[b] = ring[p & 3][b];
-#ifdef NERF_EXP_FWD_NOWLOAD
-    if (false) {
-#else
     if (p + 4 < KS) {
-#endif
-      const int kk = kpos<KIND>(p + 4, w);
 #pragma unroll
-      for (int b = 0; b < NBW; ++b) ring[p & 3][b] = frag_ld(rs, wcur, nb0 + b, kk, KS, lane);
+      for (int b = 0; b < NBW; ++b) ring[p & 3][b] = frag_ld(rs, wcur, nb0 + b, p + 4, KS, lane);
     } else if (p + 4 - KS < KSN) {
-      const int kk = kpos<KINDN>(p + 4 - KS, w);
 #pragma unroll
-      for (int b = 0; b < NBWN; ++b) ring[p & 3][b] = frag_ld(rs, wnext, nbn0 + b, kk, KSN, lane);
+      for (int b = 0; b < NBWN; ++b) ring[p & 3][b] = frag_ld(rs, wnext, nbn0 + b, p + 4 - KS, KSN, lane);
     }
-#ifdef NERF_EXP_FWD_NOMFMA
-#pragma unroll
-    for (int a = 0; a < TA; ++a) asm volatile("" ::"v"(af[a]));
-#pragma unroll
-    for (int b = 0; b < NBW; ++b) asm volatile("" ::"v"(bf[b]));
-#else
 #pragma unroll
     for (int a = 0; a < TA; ++a)
 #pragma unroll
       for (int b = 0; b < NBW; ++b)
         acc[a][b] = h16_mfma(bf[b], af[a], acc[a][b]);
-#endif
-    if (p + 1 < KS && p + 1 != BAR) {
+    if (p + 1 < KS) {
 #pragma unroll
       for (int a = 0; a < TA; ++a) af[a] = an[a];
     }
@@ -300,13 +264,12 @@ __device__ __forceinline__ uint32_t relu_pk(float x, float y) {
   return __builtin_bit_cast(uint32_t, r);
 }
 
-// fp16 build: the output pair of accumulator registers (r, r + 1) — both fp16-rounded in one v_cvt_pk_f16_f32,
-// widened, the fp32 bias pair added in one v_pk_add_f32 — then relu_pk.  (hipcc had already paired the scalar form
-// the same way; written on pairs, 5 spilled VGPRs went away and the time stayed: 750 us per training launch against
-// 656 us for the bf16 build, whose bias sits in the accumulators — profiles/r05/prof_amp_summary.txt)
-// bf16 build: relu_pk of the accumulators.
+// fp16 build: the output pair of accumulator registers (r, r + 1) — both fp16-rounded in one v_cvt_pk_f16_f32, the
+// fp32 bias added to each widened value — then relu_pk.  (Written on pairs, 5 spilled VGPRs went away and the time
+// stayed: 750 us per training launch against 656 us for the bf16 build, whose bias sits in the accumulators —
+// profiles/r05/prof_amp_summary.txt)  bf16 build: relu_pk of the accumulators.
 __device__ __forceinline__ uint32_t relu_pk_out(float a0, float a1, float b0, float b1) {
-#if NERF_F16 && !defined(NERF_F16_NOMIX)
+#if NERF_F16
   // fp32(fp16 value) + bias in ONE v_fma_mix_f32 per element (f16 source x 1.0 + f32 bias, one fp32 rounding of the
   // exact sum = the fp32 add), instead of a widening convert + half a v_pk_add_f32: hipcc folds fmaf(x, 1, b) into an
   // add and never selects the mixed form
@@ -315,10 +278,6 @@ __device__ __forceinline__ uint32_t relu_pk_out(float a0, float a1, float b0, fl
   asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(z0) : "v"(hb), "v"(b0));
   asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(z1) : "v"(hb), "v"(b1));
   return relu_pk(z0, z1);
-#elif NERF_F16
-  const nerf_f16x2 h = __builtin_convertvector(nerf_f32x2{a0, a1}, nerf_f16x2);
-  const nerf_f32x2 x = __builtin_convertvector(h, nerf_f32x2) + nerf_f32x2{b0, b1};
-  return relu_pk(x[0], x[1]);
 #else
   return relu_pk(a0, a1);
 #endif
@@ -327,13 +286,6 @@ __device__ __forceinline__ uint32_t relu_pk_out(float a0, float a1, float b0, fl
 template <int TA, int NB>
 __device__ __forceinline__ void relu_to_lds(const nerf_f32x16 (&acc)[4][2], nerf_bf16* dst, int pitch, int ar0, int c0,
                                             int li, int lh, const float* bias) {
-#ifdef NERF_EXP_FWD_NOEPI
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) asm volatile("" ::"v"(acc[a][b]));
-  return;
-#endif
 #pragma unroll
   for (int a = 0; a < TA; ++a) {
     const int r = ar0 + 32 * a + li;
@@ -434,14 +386,9 @@ constexpr int64_t frag_off(int t) {
 // io wave j: copy rows 32 j .. 32 j + 31 of an LDS tile (COLS bf16 wide, pitch) to global rows m0 + r (ld); with
 // MB, also the ReLU bitmask word of every 32 columns (bit = value > 0) to MB[(m0 + r) * (COLS / 32) + g]
 typedef unsigned int nerf_u32x4t __attribute__((ext_vector_type(4)));
-template <int COLS, bool MASK_>
+template <int COLS, bool MASK>
 __device__ __forceinline__ void io_copy(const nerf_bf16* src, int pitch, nerf_bf16* __restrict__ dst, int64_t ld,
                                         int64_t m0, uint32_t* __restrict__ mb, int j, int lane) {
-#ifdef NERF_EXP_NOMASK
-  constexpr bool MASK = false;
-#else
-  constexpr bool MASK = MASK_;
-#endif
   constexpr int CH = COLS / 8, RPI = 64 / CH, IT = 32 / RPI, B = IT < 8 ? IT : 8;
   const int rl = lane / CH, c = lane - rl * CH;
 #pragma unroll
@@ -455,15 +402,9 @@ __device__ __forceinline__ void io_copy(const nerf_bf16* src, int pitch, nerf_bf
 #pragma unroll
     for (int i = 0; i < B; ++i) {
       const int64_t m = m0 + 32 * j + (i0 + i) * RPI + rl;
-#ifdef NERF_EXP_NOSTORE
-      if (v[i].x == 0x12345678u && v[i].y == 0x9abcdef0u) *reinterpret_cast<uint4*>(dst + m * ld + 8 * c) = v[i];
-#elif defined(NERF_IO_PLAIN_STORES)
-      *reinterpret_cast<uint4*>(dst + m * ld + 8 * c) = v[i];
-#else
       // non-temporal: the saved activations are read back only by the backward, long after (measured on the fine-net
       // training forward: 1.27 -> 1.06 ms against plain stores)
       __builtin_nontemporal_store(__builtin_bit_cast(nerf_u32x4t, v[i]), reinterpret_cast<nerf_u32x4t*>(dst + m * ld + 8 * c));
-#endif
       if (MASK) {
         // post-ReLU bf16: bit = value != 0 (a -0 is 0x8000); 2 values per v_pk_min_u16, quads combined by DPP
         const uint32_t u[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
@@ -578,12 +519,7 @@ __device__ __forceinline__ void io_role(const FusedArgs& A, nerf_bf16* Hs, nerf_
         cin.store(Es, EP, j, lane);
         if (next) io_encode<true>(enc, A.xd, A.M, m0 + (int64_t)G * BMF, j, lane, A.X3E);
       }
-#ifdef NERF_EXP_ODD_NOSTORE
-      // probe of the odd-layer recompute: X1, X3, X5, X7 (epilogues k = 0, 2, 4, 6) not saved
-      if (TRAIN && (k & 1)) {
-#else
       if (TRAIN) {
-#endif
         nerf_bf16* Y = (k == 3) ? A.X3E : A.Y + (int64_t)(k < 3 ? k : k - 1) * Mp * 256;
         io_copy<256, MASKS>(Hs + (k & 1) * BMF * HP, HP, Y, k == 3 ? 320 : 256, m0, MASKS ? A.MB + (int64_t)k * Mp * 8 : nullptr, j,
                             lane);
@@ -625,36 +561,36 @@ __device__ __forceinline__ void compute_role(const FusedArgs& A, nerf_bf16* Hs, 
   };
   for (int t = tile; t < A.ntiles; t += G) {
     const int64_t m0 = (int64_t)t * BMF;
-    // trunk: <KS, NBW, TA, KIND, ESRC, BAR, KSN, NBWN, KINDN>; epilogue k -> H[k & 1]
+    // trunk: <KS, NBW, TA, SRC, BAR, KSN, NBWN>; epilogue k -> H[k & 1]
     bias_trunk(0);
-    stage<4, 2, 4, K_ID, 1, -1, 16, 2, K_ROT16>(acc, ring, rs, F(0), 2 * w, F(1), 2 * w, H1, Es, HP, EP, 0, li, lh, lane, w);
+    stage<4, 2, 4, SRC_E, false, 16, 2>(acc, ring, rs, F(0), 2 * w, F(1), 2 * w, H1, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H0, HP, 0, 64 * w, li, lh, BI(0));
     bias_trunk(1);
-    stage<16, 2, 4, K_ROT16, 0, 4, 16, 2, K_ROT16>(acc, ring, rs, F(1), 2 * w, F(2), 2 * w, H0, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 16, 2>(acc, ring, rs, F(1), 2 * w, F(2), 2 * w, H0, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H1, HP, 0, 64 * w, li, lh, BI(1));
     bias_trunk(2);
-    stage<16, 2, 4, K_ROT16, 0, 4, 16, 2, K_ROT16>(acc, ring, rs, F(2), 2 * w, F(3), 2 * w, H1, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 16, 2>(acc, ring, rs, F(2), 2 * w, F(3), 2 * w, H1, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H0, HP, 0, 64 * w, li, lh, BI(2));
     bias_trunk(3);
-    stage<16, 2, 4, K_ROT16, 0, 4, 20, 2, K_L4>(acc, ring, rs, F(3), 2 * w, F(4), 2 * w, H0, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 20, 2>(acc, ring, rs, F(3), 2 * w, F(4), 2 * w, H0, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H1, HP, 0, 64 * w, li, lh, BI(3));
     bias_trunk(4);
-    stage<20, 2, 4, K_L4, 2, 8, 16, 2, K_ROT16>(acc, ring, rs, F(4), 2 * w, F(5), 2 * w, H1, Es, HP, EP, 0, li, lh, lane, w);
+    stage<20, 2, 4, SRC_L4, true, 16, 2>(acc, ring, rs, F(4), 2 * w, F(5), 2 * w, H1, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H0, HP, 0, 64 * w, li, lh, BI(4));
     bias_trunk(5);
-    stage<16, 2, 4, K_ROT16, 0, 4, 16, 2, K_ROT16>(acc, ring, rs, F(5), 2 * w, F(6), 2 * w, H0, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 16, 2>(acc, ring, rs, F(5), 2 * w, F(6), 2 * w, H0, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H1, HP, 0, 64 * w, li, lh, BI(5));
     bias_trunk(6);
-    stage<16, 2, 4, K_ROT16, 0, 4, 16, 2, K_ROT16>(acc, ring, rs, F(6), 2 * w, F(7), 2 * w, H1, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 16, 2>(acc, ring, rs, F(6), 2 * w, F(7), 2 * w, H1, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H0, HP, 0, 64 * w, li, lh, BI(6));
     bias_trunk(7);
     // the head's fragments are one 32-column block shared by every wave (nb 0)
-    stage<16, 2, 4, K_ROT16, 0, 4, 16, 1, K_ROT16>(acc, ring, rs, F(7), 2 * w, F(8), 0, H0, Es, HP, EP, 0, li, lh, lane, w);
+    stage<16, 2, 4, SRC_H, true, 16, 1>(acc, ring, rs, F(7), 2 * w, F(8), 0, H0, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 2>(acc, H1, HP, 0, 64 * w, li, lh, BI(7));
 
-    // ---- head: O16 = h7 W_head^T + b (sigma | 15 geo | 0), wave w -> rows 32w..32w+31 (own trunk.7 columns first)
+    // ---- head: O16 = h7 W_head^T + b (sigma | 15 geo | 0), wave w -> rows 32w..32w+31
     acc_bias(acc[0][0], BI(8), 0, lh);
-    stage<16, 1, 1, K_ROT16, 0, 4, 4, 1, K_ID>(acc, ring, rs, F(8), 0, F(9), w, H1, Es, HP, EP, 32 * w, li, lh, lane, w);
+    stage<16, 1, 1, SRC_H, true, 4, 1>(acc, ring, rs, F(8), 0, F(9), w, H1, Es, HP, EP, 32 * w, li, lh, lane);
     const int r = 32 * w + li;
     if (lh == 0) Ssig[r] = acc_out(acc[0][0], 0, BI(8), 0, lh);
 #pragma unroll
@@ -669,13 +605,13 @@ __device__ __forceinline__ void compute_role(const FusedArgs& A, nerf_bf16* Hs, 
     // ---- colour layer 0: C0 = ReLU(CIN W_c0^T + b), wave w -> cols 32w..32w+31 of all rows, tile in H[1] (pitch CP)
 #pragma unroll
     for (int a = 0; a < 4; ++a) acc_bias(acc[a][0], BI(9), 32 * w, lh);
-    stage<4, 1, 4, K_ID, 1, -1, 8, 1, K_ROT8>(acc, ring, rs, F(9), w, F(10), 0, H1, Es, HP, EP, 0, li, lh, lane, w);
+    stage<4, 1, 4, SRC_E, false, 8, 1>(acc, ring, rs, F(9), w, F(10), 0, H1, Es, HP, EP, 0, li, lh, lane);
     relu_to_lds<4, 1>(acc, H1, CP, 0, 32 * w, li, lh, BI(9));
 
-    // ---- colour out: O3 = C0 W_c1^T + b, wave w -> rows 32w..32w+31 (barrier C after its own 2 k-steps);
+    // ---- colour out: O3 = C0 W_c1^T + b, wave w -> rows 32w..32w+31 (barrier C before it);
     // the next tile's trunk.0 fragments are prefetched into the ring
     acc_bias(acc[0][0], BI(10), 0, lh);
-    stage<8, 1, 1, K_ROT8, 0, 2, 4, 2, K_ID>(acc, ring, rs, F(10), 0, F(0), 2 * w, H1, Es, CP, EP, 32 * w, li, lh, lane, w);
+    stage<8, 1, 1, SRC_H, true, 4, 2>(acc, ring, rs, F(10), 0, F(0), 2 * w, H1, Es, CP, EP, 32 * w, li, lh, lane);
     const int64_t m = m0 + r;
     if (lh == 0) {
       const float sraw = Ssig[r];

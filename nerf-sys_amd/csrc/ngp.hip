@@ -1697,15 +1697,6 @@ extern "C" int nerf_hash_encode(const NerfHashGrid* grid, const float* table, co
   return nerf_launch_status();
 }
 
-// -DNERF_HASH_BWD_NOAGG builds the per-(sample, level) kernel without run aggregation (tools/ A/B builds)
-static constexpr bool hash_bwd_aggregate() {
-#ifdef NERF_HASH_BWD_NOAGG
-  return false;
-#else
-  return true;
-#endif
-}
-
 extern "C" int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* x, int64_t x_stride, int64_t M,
                                     const float* aabb, float enc_eps, const float* d_out, int d_stride,
                                     float* d_table, hipStream_t st) {
@@ -1724,7 +1715,7 @@ extern "C" int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* x, in
   switch (a.F) {
     case 1: hash_bwd_kernel<1><<<blocks, 256, 0, st>>>(a, x, x_stride, M, d_out, d_stride, d_table); break;
     case 2:
-      if (a.interp != 0 && hash_bwd_aggregate())
+      if (a.interp != 0)  // nearest-neighbour interpolation: the per-(sample, level) kernel, no run aggregation
         hash_bwd_f2_agg_kernel<<<(unsigned)nerf_cdiv(4 * M, 256), 256, 0, st>>>(a, x, x_stride, M, d_out, d_stride,
                                                                                 d_table);
       else
