@@ -215,7 +215,7 @@ int nerf_composite_bwd(const float* rgb_sigma, const float* t, const float* bg, 
 /* ------------------------------------------------------------------ optimiser */
 
 /* Per-block partial sums of squares of g (n) into partials[256] (first pass of
- * clip_grad_norm_, pipelines/online_stage/runtime_adapt.py:305-307). */
+ * clip_grad_norm_, pipelines/online_stage/runtime_adapt.py:305-307).  n == 0 (g may be NULL) writes 256 zeros. */
 int nerf_grad_sqnorm(const float* g, int64_t n, float* partials, hipStream_t stream);
 
 /* torch.optim.Adam step (common/utils.py:16-76 param groups) over a flat buffer split into

@@ -156,7 +156,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }  // namespace
 
 extern "C" int nerf_grad_sqnorm(const float* g, int64_t n, float* partials, hipStream_t stream) {
-  NERF_CHECK_ARG(g && partials && n >= 0);
+  // an empty gradient has no storage (torch hands out NULL for it): the kernel reads nothing and writes 256 zeros
+  NERF_CHECK_ARG((g || n == 0) && partials && n >= 0);
   sqnorm_kernel<<<NPART, 1024, 0, stream>>>(g, n, partials);
   return nerf_launch_status();
 }
