@@ -55,7 +55,9 @@ int nerf_pick_pixels_dseed(int64_t n, int n_images, int H, int W, uint64_t seed_
                            const int64_t* step_dev, int32_t* pix_out, hipStream_t stream);
 
 /* clamp_rays_near_far (nerfs/ray_sampling.py:139-176), in place; valid_out (n) bytes or NULL.
- * has_near/has_far select the overrides. */
+ * has_near/has_far select the overrides.  Here and in nerf_rays_ndc, nerf_sample_stratified, nerf_build_xd,
+ * nerf_sample_pdf and nerf_freq_encode n == 0 is an empty call: the scalar arguments are still checked, the buffers
+ * may be NULL. */
 int nerf_clamp_near_far(float* rays, int64_t n, int has_near, float near_v, int has_far, float far_v,
                         float eps, float invalid_value, uint8_t* valid_out, hipStream_t stream);
 
@@ -86,7 +88,8 @@ int nerf_sample_pdf(const float* t, const float* w, int64_t n, int S, int n_imp,
 /* ------------------------------------------------------------------ encoding */
 
 /* FrequencyEncoder.torch_forward (models/encodings.py:437-444): out (n, D*(2L+inc)) with row
- * stride ld_out floats; per dim [cos 2^0..2^{L-1}, sin ...] after the optional raw input. */
+ * stride ld_out floats; per dim [cos 2^0..2^{L-1}, sin ...] after the optional raw input.  L = 0 without the input
+ * has no output element: an empty call as well. */
 int nerf_freq_encode(const float* x, int64_t n, int D, int L, int include_input, float* out, int ld_out,
                      hipStream_t stream);
 

@@ -311,8 +311,9 @@ extern "C" int nerf_pick_pixels_dseed(int64_t n, int n_images, int H, int W, uin
 
 extern "C" int nerf_clamp_near_far(float* rays, int64_t n, int has_near, float near_v, int has_far, float far_v,
                                    float eps, float invalid_value, uint8_t* valid_out, hipStream_t stream) {
-  NERF_CHECK_ARG(rays && n >= 0);
-  if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(n >= 0);
+  if (n == 0) return NERF_OK;  // torch hands out NULL for an empty tensor
+  NERF_CHECK_ARG(rays);
   clamp_kernel<<<blocks_for(n, 256), 256, 0, stream>>>(rays, n, has_near, near_v, has_far, far_v, eps,
                                                         invalid_value, valid_out);
   return nerf_launch_status();
@@ -320,33 +321,37 @@ extern "C" int nerf_clamp_near_far(float* rays, int64_t n, int has_near, float n
 
 extern "C" int nerf_rays_ndc(const float* rays_in, int64_t n, int H, int W, float focal, float near_plane,
                              float* rays_out, hipStream_t stream) {
-  NERF_CHECK_ARG(rays_in && rays_out && n >= 0 && H > 0 && W > 0 && focal > 0.f);
+  NERF_CHECK_ARG(n >= 0 && H > 0 && W > 0 && focal > 0.f);
   if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(rays_in && rays_out);
   ndc_kernel<<<blocks_for(n, 256), 256, 0, stream>>>(rays_in, n, (float)H, (float)W, focal, near_plane, rays_out);
   return nerf_launch_status();
 }
 
 extern "C" int nerf_sample_stratified(const float* rays, int64_t n, int S, int randomized, const float* u,
                                       uint64_t seed, float* t_out, hipStream_t stream) {
-  NERF_CHECK_ARG(rays && t_out && n >= 0 && S >= 1);
+  NERF_CHECK_ARG(n >= 0 && S >= 1);
   if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(rays && t_out);
   stratified_kernel<<<blocks_for(n * S, 256), 256, 0, stream>>>(rays, n, S, randomized, u, seed, t_out);
   return nerf_launch_status();
 }
 
 extern "C" int nerf_build_xd(const float* rays, const float* t, int64_t n, int S, float* xd_out,
                              hipStream_t stream) {
-  NERF_CHECK_ARG(rays && t && xd_out && n >= 0 && S >= 1);
+  NERF_CHECK_ARG(n >= 0 && S >= 1);
   if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(rays && t && xd_out);
   build_xd_kernel<<<blocks_for(n * S, 256), 256, 0, stream>>>(rays, t, n, S, xd_out);
   return nerf_launch_status();
 }
 
 extern "C" int nerf_freq_encode(const float* x, int64_t n, int D, int L, int include_input, float* out, int ld_out,
                                 hipStream_t stream) {
-  NERF_CHECK_ARG(x && out && n >= 0 && D >= 1 && L >= 0 && L <= 24);
+  NERF_CHECK_ARG(n >= 0 && D >= 1 && L >= 0 && L <= 24);
   NERF_CHECK_ARG(ld_out >= D * (2 * L + (include_input ? 1 : 0)));
-  if (n == 0) return NERF_OK;
+  if (n == 0 || (L == 0 && !include_input)) return NERF_OK;  // nothing to write: the output has no element
+  NERF_CHECK_ARG(x && out);
   freq_encode_kernel<<<blocks_for(n * D, 256), 256, 0, stream>>>(x, n, D, L, include_input, out, ld_out);
   return nerf_launch_status();
 }

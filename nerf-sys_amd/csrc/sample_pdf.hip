@@ -141,8 +141,9 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
 
 extern "C" int nerf_sample_pdf(const float* t, const float* w, int64_t n, int S, int n_imp, const float* u, int det,
                                uint64_t seed, float* t_out, hipStream_t stream) {
-  NERF_CHECK_ARG(t && w && t_out && n >= 0 && S >= 3 && S <= MAXS && n_imp >= 1 && S + n_imp <= 512);
-  if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(n >= 0 && S >= 3 && S <= MAXS && n_imp >= 1 && S + n_imp <= 512);
+  if (n == 0) return NERF_OK;  // an empty batch has no buffers: torch hands out NULL for an empty tensor
+  NERF_CHECK_ARG(t && w && t_out);
   const int tot = S + n_imp;
   const unsigned blocks = (unsigned)nerf_cdiv(n, 4);
   if (tot <= 64) sample_pdf_kernel<1><<<blocks, 256, 0, stream>>>(t, w, n, S, n_imp, u, det, seed, t_out);
