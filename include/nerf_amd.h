@@ -152,6 +152,14 @@ int nerf_mlp_bwd_2s(const float* w, int64_t M, const float* d_rgb_sigma, float* 
  * that biased the long signed input-gradient chain (weight gradients 1.3-20x the fp32 engine's error); with separate
  * small-term accumulators they are as accurate as the fp32 engine's (tests/test_gpu_split_gemm.py). */
 #define NERF_MLP_NATIVE_DGRAD 2
+/* NERF_MLP_FWD_LAYERED (forward, with the split engine): one GEMM launch per trunk layer.  By default the split
+ * forward is four launches — xyz encoding, weight piece planes, ONE chained launch that carries every 256-row tile
+ * through the eight trunk layers, and the head / colour tail — in training and in eval.  The chained launch runs the
+ * per-layer kernel's tile code once per layer, so every stored value (activations, ReLU mask words) is bitwise the
+ * layered form's (tests/test_gpu_fwd_chain.py).  A call with events != NULL also runs the eight launches, because an
+ * event pair brackets one layer's launch: per-layer timings are always those of a layer launched alone.  No effect
+ * with NERF_MLP_NATIVE_FP32.  nerf_mlp_bwd_ex does not know this bit (NERF_E_ENUM). */
+#define NERF_MLP_FWD_LAYERED 4
 int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, float* rgb_sigma, void* ws, int64_t ws_bytes,
                     int training, int flags, hipEvent_t* events, hipStream_t stream);
 int nerf_mlp_bwd_ex(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w, int accumulate, void* ws,

@@ -111,11 +111,29 @@ static __global__ void x6_planes_kernel(X6Jobs jobs) {
 // (profiles/r04/x6_epilogue_ab.txt): fwd 0.625 -> 0.591 ms, dgrad 0.669 -> 0.610 ms per fine layer.
 constexpr int X6E_PITCH = 36;
 constexpr int X6E_WAVE_FLOATS = 32 * X6E_PITCH;
-template <int TM, int TN, int EPI>
+// a's upper 32 lanes <-> b's lower 32 lanes (v_permlane32_swap).  The pair's elements go through scalar temporaries:
+// __builtin_bit_cast applied directly to an element expression (bit_cast(float, r[1])) read element 0 with this clang.
+__device__ __forceinline__ void x6_swap32(float& a, float& b) {
+  typedef unsigned x6_u32x2 __attribute__((ext_vector_type(2)));
+  const x6_u32x2 r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b),
+                                                      false, false);
+  const unsigned r0 = r[0], r1 = r[1];
+  a = __builtin_bit_cast(float, r0);
+  b = __builtin_bit_cast(float, r1);
+}
+
+// HAND (the chained forward, TM = 1, n0 = 0): the stored values of columns 0 .. 63 also leave in ho[2][1][2][2] as the
+// activation registers of the next layer's slabs 0 and 1 (x6w_tile's ra sets).  Lane (li, lh) holds columns
+// 8 q + 4 lh + e of block b; the A fragment of k-step ks of slab b wants lane (r, h) to hold k = 16 ks + 8 h + 0 .. 7.
+// For q0 = 2 ks, v_permlane32_swap of (q0, e) with (q0 + 1, e) swaps the first register's upper lanes with the second's
+// lower lanes: the first then holds k = 16 ks + 8 h + e and the second k = 16 ks + 8 h + 4 + e on both lane halves.
+template <int TM, int TN, int EPI, bool HAND = false>
 __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int64_t mw, int n0, int lane,
                                                 const float* __restrict__ bias, float* __restrict__ C, int ldc,
                                                 const uint32_t* __restrict__ mbits, int ldmb,
-                                                uint32_t* __restrict__ mbits_out, float* E) {
+                                                uint32_t* __restrict__ mbits_out, float* E,
+                                                float4 (*ho)[1][2][2] = nullptr, const float* bias_lds = nullptr) {
+  static_assert(!HAND || (TM == 1 && TN >= 2 && EPI == EPI_BIAS_RELU), "hand-off: the forward tile");
   const int li = lane & 31, lh = lane >> 5;
   const int rr = lane >> 3, cc = 4 * (lane & 7);  // read-back: row rr + 8 i, columns cc .. cc + 3
 #pragma unroll
@@ -126,13 +144,20 @@ __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int6
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       bv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) bv[q] = *reinterpret_cast<const float4*>(bias + nb + 8 * q + 4 * lh);
+      if constexpr (HAND) {
+        // the wave's LDS copy of the bias row: a global load here sits behind the previous block's stores in the
+        // in-order memory counter, so its wait also waits for those stores
+        bv[q] = *reinterpret_cast<const float4*>(bias_lds + nb + 8 * q + 4 * lh);
+      } else if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) {
+        bv[q] = *reinterpret_cast<const float4*>(bias + nb + 8 * q + 4 * lh);
+      }
     }
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
       const int64_t m = mw + a * 32 + li;
       uint32_t word = 0;
       if (EPI == EPI_MASK) word = mbits[m * ldmb + g];
+      float hv[4][4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float v[4];
@@ -146,8 +171,25 @@ __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int6
             word |= (v[e] > 0.f ? 1u : 0u) << (8 * q + 4 * lh + e);
           }
           if (EPI == EPI_MASK) v[e] = ((word >> (8 * q + 4 * lh + e)) & 1u) ? v[e] : 0.f;
+          if constexpr (HAND) hv[q][e] = v[e];
         }
         *reinterpret_cast<float4*>(E + li * X6E_PITCH + 8 * q + 4 * lh) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+      if constexpr (HAND) {
+        if (b < 2) {
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            float f0[4], f1[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              f0[e] = hv[2 * ks][e];
+              f1[e] = hv[2 * ks + 1][e];
+              x6_swap32(f0[e], f1[e]);
+            }
+            ho[b][0][ks][0] = make_float4(f0[0], f0[1], f0[2], f0[3]);
+            ho[b][0][ks][1] = make_float4(f1[0], f1[1], f1[2], f1[3]);
+          }
+        }
       }
       if (EPI == EPI_BIAS_RELU && mbits_out) {
         word |= __shfl_xor(word, 32, 64);
@@ -184,12 +226,25 @@ __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int6
 //   input gradient <EPI_MASK, true, 8, 4>: 256 x 128 tiles at two waves per SIMD, split accumulators (BIGSMALL below;
 //                  0.73-0.75 -> 0.665 ms per fine layer against 64-row waves at one per SIMD), K = 256 unrolled on
 //                  three activation register sets (NKC below)
-template <int EPI, bool BIGSMALL, int NKC, int TN>
-__global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __restrict__ A, int lda,
-                                                             const nerf_bf16* __restrict__ Bp, int ldb, int64_t bplane,
-                                                             const float* __restrict__ bias, float* __restrict__ C,
-                                                             int ldc, const uint32_t* __restrict__ mbits, int ldmb,
-                                                             uint32_t* __restrict__ mbits_out, int K, int n_ntiles) {
+// bf16 elements of the two weight buffers (three piece images of [32 TN][32] each)
+template <int TN>
+constexpr int x6w_smem_elems() { return 2 * 3 * (32 * TN) * 32; }
+
+// One output tile — rows m0 .. m0 + 255, columns n0 .. n0 + 32 TN - 1 — by the whole workgroup: the slab loop and the
+// epilogue.  smem: the workgroup's x6w_smem_elems<TN>() bf16.  Called once per launch by gemm_nt_x6w_kernel (CH = 0)
+// and once per layer by gemm_nt_x6w_chain_kernel (CH = 1).  There `first` marks the chain's first layer; every later
+// one finds its slabs 0 and 1 in ra[0] / ra[1] (the previous layer's epilogue left them there) and its slab-0 weights
+// already in buffer 0, and skips the prologue.  nBp / nldb / nbplane (CH = 1): the next layer's weight planes, nBp ==
+// nullptr after the last layer.
+template <int EPI, bool BIGSMALL, int NKC, int TN, int CH = 0>
+__device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, const nerf_bf16* __restrict__ Bp,
+                                         int ldb, int64_t bplane, const float* __restrict__ bias,
+                                         float* __restrict__ C, int ldc, const uint32_t* __restrict__ mbits, int ldmb,
+                                         uint32_t* __restrict__ mbits_out, int K, int64_t m0, int n0,
+                                         nerf_bf16* smem, float4 (&ra)[NKC > 0 ? 3 : 2][1][2][2],
+                                         const nerf_bf16* nBp = nullptr, int nldb = 0, int64_t nbplane = 0,
+                                         bool first = true) {
+  static_assert(CH == 0 || (NKC == 0 && EPI == EPI_BIAS_RELU), "chained: the forward tile");
   constexpr int BK = 32, NW = 8, TM = 1;          // slab depth, waves, 32-row blocks per wave
   constexpr int WTM = 32 * TM, BM = WTM * NW, BN = 32 * TN;
   constexpr int KS = BK / 16;                     // MFMA k-steps per slab
@@ -203,12 +258,12 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   constexpr int PL = BN * LS;
   // the epilogue tiles reuse the two weight buffers
   static_assert(2 * 3 * PL >= NW * X6E_WAVE_FLOATS * 2, "epilogue tiles");
-  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[2 * 3 * PL];
+  // chained: buffer 0 receives the next layer's slab 0 during the last slab, so the tiles take buffer 1 alone
+  // ... followed by one copy of the layer's bias row (BN floats) per wave
+  static_assert(CH == 0 || 3 * PL >= NW * (X6E_WAVE_FLOATS + BN) * 2, "epilogue tiles and bias rows in buffer 1");
+  static_assert(CH == 0 || BN == 256, "bias row: one float4 per lane");
+  static_assert(2 * 3 * PL == x6w_smem_elems<TN>(), "weight buffers");
 
-  const int tile = xcd_remap(blockIdx.x, gridDim.x);
-  const int mt = tile / n_ntiles, nt = tile - mt * n_ntiles;
-  const int64_t m0 = (int64_t)mt * BM;
-  const int n0 = nt * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const nerf_bf16* Bb = Bp + (int64_t)n0 * ldb;
@@ -221,7 +276,6 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   // loads are issued at the start of slab kt, after its weight DMA, so the end-of-slab weight wait leaves them in
   // flight (two slabs of latency instead of one; profiles/r04/x6_a3_ab.txt: 0.597 -> 0.584 ms per fine launch)
   constexpr bool A3 = NKC > 0;
-  float4 ra[A3 ? 3 : 2][TM][KS][2];
   // the weight slab is DMA'd straight into the LDS image (global_load_lds_dwordx4, no VGPRs): one wave-instruction
   // fills 16 rows x 64 B of a piece image, lane l -> row l / 4, slot l % 4, so the swizzle goes on the source: lane l
   // reads chunk (l % 4) ^ ((row >> 2) & 3) = (l & 3) ^ ((l >> 4) & 3) of its row.  Issued as inline asm after the touch
@@ -233,6 +287,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   static_assert(GPW * NW == 3 * GPP && GPP * 1024 == BN * BK * 2, "weight staging");
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t gofs = (uint32_t)((((lane >> 2) * ldb) + 8 * ((lane & 3) ^ ((lane >> 4) & 3))) * 2);
+  const uint32_t ngofs = (uint32_t)((((lane >> 2) * nldb) + 8 * ((lane & 3) ^ ((lane >> 4) & 3))) * 2);
+  const nerf_bf16* nBb = nBp + (int64_t)n0 * nldb;
   const uint32_t smem_u32 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
 #define X6W_ALOAD(set_, k0_)                                                                              \
   _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                         \
@@ -245,7 +301,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   // dgrad 0.59 -> 0.67 ms (profiles/r04/x6_pingpong_ab.txt)
   constexpr int BPG = 2;
   // slab k0_'s weight DMA into buffer dbuf_, after the touch of activation set j
-#define X6W_BLOAD(k0_, dbuf_)                                                                             \
+#define X6W_BLOAD(k0_, dbuf_) X6W_BLOAD_SRC(Bb, ldb, bplane, gofs, k0_, dbuf_)
+#define X6W_BLOAD_SRC(Bb_, ldb_, bplane_, gofs_, k0_, dbuf_)                                              \
   {                                                                                                       \
     _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                       \
       _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                  \
@@ -253,11 +310,11 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
                      "v"(__builtin_bit_cast(x6_f32x4, ra[j][a][ks][1])) : "memory");                     \
     _Pragma("unroll") for (int i = 0; i < GPW; ++i) {                                                    \
       const int g_ = wave_u + NW * i, p_ = g_ / GPP, rb_ = (g_ % GPP) * 16;                              \
-      const nerf_bf16* sb_ = Bb + p_ * bplane + (int64_t)rb_ * ldb + (k0_);                              \
+      const nerf_bf16* sb_ = (Bb_) + p_ * (bplane_) + (int64_t)rb_ * (ldb_) + (k0_);                     \
       const uint32_t dst_ = smem_u32 + (uint32_t)((((dbuf_) * 3 + p_) * PL + rb_ * LS) * 2);             \
       unsigned keep_;                                                                                     \
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t" \
-                   "s_mov_b32 m0, %0" : "=&s"(keep_) : "v"(gofs), "s"(sb_), "s"(dst_) : "memory");       \
+                   "s_mov_b32 m0, %0" : "=&s"(keep_) : "v"(gofs_), "s"(sb_), "s"(dst_) : "memory");      \
     }                                                                                                     \
   }
   // the weight DMA done: the four activation loads (TM KS 2) issued after it stay in flight
@@ -278,14 +335,18 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
       }
 
   const int nk = A3 ? NKC : K / BK;
-  X6W_ALOAD(0, 0);
-  X6W_ALOAD(1, (nk > 1 ? 1 : 0) * BK);
-  {
-    const int j = 0;
-    X6W_BLOAD(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  float4 bz = make_float4(0.f, 0.f, 0.f, 0.f);  // chained: this lane's four values of the bias row, for the epilogue
+  if constexpr (CH != 0) bz = *reinterpret_cast<const float4*>(bias + n0 + 4 * lane);
+  if (CH == 0 || first) {
+    X6W_ALOAD(0, 0);
+    X6W_ALOAD(1, (nk > 1 ? 1 : 0) * BK);
+    {
+      const int j = 0;
+      X6W_BLOAD(0, 0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
   }
-  __syncthreads();
   // one slab's k-steps on activation register set rj and weight buffer S
   auto slab_mfma = [&](const float4 (&rj)[TM][KS][2], const nerf_bf16* S, auto&& after_split) __attribute__((always_inline)) {
 #pragma unroll
@@ -299,6 +360,16 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
             af[a][0] = __builtin_bit_cast(nerf_bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
             af[a][1] = __builtin_bit_cast(nerf_bf16x8, make_uint4(m0_.x, m0_.y, m1.x, m1.y));
             af[a][2] = __builtin_bit_cast(nerf_bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
+          }
+          // ... and their pieces computed: without this touch the scheduler may leave part of the last k-step's split
+          // after after_split's loads, the old and new values of a set then interfere, and the allocator gives the loads
+          // other registers and copies them at the end of the round — behind a vmcnt(0) that drains the loads in flight
+          // (seen in the chained kernel: 8 v_mov_b64 and the drain per round)
+          if constexpr (CH != 0) {
+            if (ks == KS - 1) {
+#pragma unroll
+              for (int a = 0; a < TM; ++a) asm volatile("" ::"v"(af[a][0]), "v"(af[a][1]), "v"(af[a][2]) : "memory");
+            }
           }
           if (ks == KS - 1) after_split();  // the slab's activation registers are all split
 #pragma unroll
@@ -355,7 +426,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
         // nk is even (host: K % (2 BK) == 0), so no guard — every path into the loop header then has the same loads in
         // flight and the compiler's counted wait there stays vmcnt(8) instead of draining to vmcnt(0)
         const int kt = kt0 + j;
-        X6W_BLOAD((kt + 1 < nk ? kt + 1 : kt) * BK, j ^ 1);
+        if (CH != 0 && j == 1) {
+          // chained: the last slab (always an odd one) fetches the NEXT layer's slab 0 instead of its own slab again;
+          // it lands in buffer 0 behind this slab's wait and barrier like any other slab
+          const bool nx = nBp != nullptr && kt + 1 >= nk;
+          X6W_BLOAD_SRC((nx ? nBb : Bb), (nx ? nldb : ldb), (nx ? nbplane : bplane), (nx ? ngofs : gofs),
+                        (nx ? 0 : (kt + 1 < nk ? kt + 1 : kt) * BK), j ^ 1);
+        } else {
+          X6W_BLOAD((kt + 1 < nk ? kt + 1 : kt) * BK, j ^ 1);
+        }
         // set j's next loads issued right after its last split, pinned before the last k-step's MFMAs
         // (profiles/r04/x6_early_a_ab.txt: fwd 0.582 -> 0.578 ms, C2 +0.5 %)
         slab_mfma(ra[j], smem + j * 3 * PL, [&] {
@@ -374,6 +453,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   }
 #undef X6W_ALOAD
 #undef X6W_BLOAD
+#undef X6W_BLOAD_SRC
 #undef X6W_BWAIT
 
   if constexpr (BIGSMALL) {
@@ -384,8 +464,92 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __rest
   }
   // the loop's last barrier freed the weight images: every wave stages its 32 x 32 blocks through a private LDS
   // tile and stores whole 128-B row lines (8 lanes per row; x6_epilogue_lds)
-  x6_epilogue_lds<TM, TN, EPI>(acc, m0 + wave * WTM, n0, lane, bias, C, ldc, mbits, ldmb, mbits_out,
-                               reinterpret_cast<float*>(smem) + wave * X6E_WAVE_FLOATS);
+  float* Eb = nullptr;  // chained: this wave's copy of the bias row, behind the eight tiles in buffer 1
+  if constexpr (CH != 0) {
+    Eb = reinterpret_cast<float*>(smem + 3 * PL) + NW * X6E_WAVE_FLOATS + wave * BN - n0;
+    *reinterpret_cast<float4*>(Eb + n0 + 4 * lane) = bz;
+  }
+  x6_epilogue_lds<TM, TN, EPI, CH != 0>(acc, m0 + wave * WTM, n0, lane, bias, C, ldc, mbits, ldmb, mbits_out,
+                                        reinterpret_cast<float*>(smem + (CH != 0 ? 3 * PL : 0)) + wave * X6E_WAVE_FLOATS,
+                                        CH != 0 ? &ra[0] : nullptr, Eb);
+}
+
+template <int EPI, bool BIGSMALL, int NKC, int TN>
+__global__ __launch_bounds__(512, 1) void gemm_nt_x6w_kernel(const float* __restrict__ A, int lda,
+                                                             const nerf_bf16* __restrict__ Bp, int ldb, int64_t bplane,
+                                                             const float* __restrict__ bias, float* __restrict__ C,
+                                                             int ldc, const uint32_t* __restrict__ mbits, int ldmb,
+                                                             uint32_t* __restrict__ mbits_out, int K, int n_ntiles) {
+  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[x6w_smem_elems<TN>()];
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int mt = tile / n_ntiles, nt = tile - mt * n_ntiles;
+  float4 ra[NKC > 0 ? 3 : 2][1][2][2];  // the activation register sets
+  x6w_tile<EPI, BIGSMALL, NKC, TN>(A, lda, Bp, ldb, bplane, bias, C, ldc, mbits, ldmb, mbits_out, K, (int64_t)mt * 256,
+                                   nt * 32 * TN, smem, ra);
+}
+
+// ------------------------------------------------------------------------------------------ chained forward
+// The trunk forward is row-local: in the forward tile above a workgroup owns 256 rows x all 256 columns and each wave
+// 32 whole rows, so the rows a wave loads for layer i + 1 are the rows it stored itself for layer i.  One launch
+// therefore carries every 256-row tile through all the layers: the same x6w_tile per layer (the same MFMA sequence on
+// every accumulator, bitwise the per-layer launches' outputs; tests/test_gpu_fwd_chain.py), the layers read from a
+// by-value table that the kernel only reads (a write at a run-time index would move it to scratch).
+// Chaining alone was SLOWER than the eight launches (17.29 -> 17.76 ms per step).  The supposed cause (only the A/B
+// totals are measured): a layer's first activation loads read what the epilogue has just stored, and its first weight
+// DMA sits behind those stores in the in-order memory counter, so every layer begins with the drain of 256 KiB of
+// stores per CU that a launch boundary hides behind the next workgroup's start.  Built on that reading, and faster
+// (profiles/fwd_chain_ab.txt):
+//   - slabs 0 and 1 of the next layer stay in registers: the epilogue leaves columns 0 .. 63 in the two activation
+//     register sets (x6_epilogue_lds HAND), which are dead during the epilogue and hold exactly two slabs;
+//   - the last slab of a layer fetches the next layer's slab-0 weights (its weight DMA would otherwise repeat its own
+//     slab), so the next layer starts computing at once and its first memory wait is one slab away.  Buffer 0 is
+//     therefore busy during the epilogue, and the epilogue tiles take buffer 1 alone (36 of its 48 KiB);
+//   - the epilogue reads the bias row from a per-wave LDS copy (8 x 1 KiB behind the tiles): in the ISA each block's
+//     global bias loads were followed by a counted wait that also covers the previous block's stores.
+// Between two layers:
+//   - one release / acquire fence pair at wavefront scope: the epilogue's stores (8 lanes per row) before the next
+//     layer's activation loads (one lane per row, slab 2 on) of the same wave.  No wave reads another wave's rows, so
+//     nothing wider is needed;
+//   - one workgroup barrier: the epilogue tiles and bias rows live in buffer 1, and the next layer's slab-1 weight DMA
+//     may land there only after every wave has read its last tile back.
+// A tile only touches its own rows of every buffer, so the eval ping-pong (a layer overwrites the buffer its
+// predecessor's input came from) works unchanged.  Layer i >= 1 must read what layer i - 1 wrote (A_i == C_{i-1},
+// lda_i == ldc_{i-1}; the host checks it).  Resources (-Rpass-analysis=kernel-resource-usage): 246 VGPRs, 89 SGPRs,
+// no scratch, 96 KiB LDS, two waves per SIMD.
+struct X6ChainLayer {
+  const float* A;        // activations in (column 0 of row 0), row pitch lda
+  const nerf_bf16* Bp;   // weight piece planes [3][256][ldb], plane stride bplane
+  const float* bias;
+  float* C;              // activations out, row pitch ldc
+  uint32_t* mbits_out;   // ReLU bitmask [M][8], nullable
+  int64_t bplane;
+  int lda, ldb, ldc, K;  // K % 64 == 0
+};
+constexpr int X6_CHAIN_MAX = 8;
+struct X6Chain {
+  X6ChainLayer l[X6_CHAIN_MAX];
+  int n;
+};
+__global__ __launch_bounds__(512, 1) void gemm_nt_x6w_chain_kernel(const X6Chain ch) {
+  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[x6w_smem_elems<8>()];
+  const int64_t m0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 256;
+  float4 ra[2][1][2][2];
+  // between two layers: the epilogue's stores before the next layer's loads of the same rows (slab 2 on), and every
+  // wave's epilogue tile (buffer 1) read back before the next layer's slab-1 weights land there
+#define X6_CHAIN_NEXT()                                        \
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       \
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       \
+  __syncthreads();
+#pragma unroll 1
+  for (int i = 0; i < ch.n; ++i) {
+    const X6ChainLayer& L = ch.l[i];
+    const X6ChainLayer& N = ch.l[i + 1 < ch.n ? i + 1 : i];
+    x6w_tile<EPI_BIAS_RELU, false, 0, 8, 1>(L.A, L.lda, L.Bp, L.ldb, L.bplane, L.bias, L.C, L.ldc, nullptr, 8,
+                                            L.mbits_out, L.K, m0, 0, smem, ra, i + 1 < ch.n ? N.Bp : nullptr, N.ldb,
+                                            N.bplane, i == 0);
+    X6_CHAIN_NEXT()
+  }
+#undef X6_CHAIN_NEXT
 }
 
 // ------------------------------------------------------------------------------------------ gemm_wgrad_x6

@@ -14,6 +14,11 @@
 //   Y0..Y2, Y4..Y7 [Mp][256], HO [Mp][4] (colour pre-activations 0..2, sigma_raw), CIN [Mp][64] (geo | dir-enc |
 //   0), C0 [Mp][128].  Backward adds dA/dB [Mp][256], dO16 [Mp][16] (from the fused colour-branch backward),
 //   transposed trunk weights, and S split-M partial slabs of the packed gradient.
+//
+// Forward launches (nerf_mlp_fwd_ex), split engine: pe_xyz, x6_planes (this call's weights as bf16 piece planes),
+// gemm_nt_x6w_chain (trunk.0 .. trunk.7 in one launch, a 256-row tile per workgroup), fwd_tail.  With
+// NERF_MLP_FWD_LAYERED or with events the trunk is eight gemm_nt_x6w launches (the chain's bitwise reference, and
+// what the per-layer event pairs time); with NERF_MLP_NATIVE_FP32: pe_xyz, eight gemm_nt16, fwd_tail.
 #include "gemm.hpp"
 #include "gemm_x6.hpp"
 #include "mlp_common.hpp"
@@ -300,8 +305,11 @@ extern "C" int64_t nerf_mlp_workspace_bytes(int64_t M, int training) {
 extern "C" int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, float* rgb_sigma, void* ws,
                                int64_t ws_bytes, int training, int flags, hipEvent_t* ev, hipStream_t st) {
   NERF_CHECK_ARG(w && ws && M >= 0 && (M == 0 || (x_d && rgb_sigma)));  // an empty batch may pass null rows
-  if (flags & ~NERF_MLP_NATIVE_FP32) return NERF_E_ENUM;
+  if (flags & ~(NERF_MLP_NATIVE_FP32 | NERF_MLP_FWD_LAYERED)) return NERF_E_ENUM;
   const bool native = flags & NERF_MLP_NATIVE_FP32;
+  // the split trunk in ONE launch (gemm_nt_x6w_chain_kernel) unless the caller asks for the per-layer launches or for
+  // their events: an event pair brackets one layer's launch
+  const bool chained = !native && !ev && !(flags & NERF_MLP_FWD_LAYERED);
   if (!nerf_aligned16(w) || !nerf_aligned16(ws) || !nerf_aligned16(rgb_sigma)) return NERF_E_ALIGN;
   const WS W = carve(ws, M, training);
   if (ws_bytes < W.bytes) return NERF_E_WORKSPACE;
@@ -320,10 +328,18 @@ extern "C" int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, floa
   // trunk
   const float* in = W.X3E + 256;
   int ld_in = 320;
+  X6Chain chain{};
   for (int i = 0; i < 8; ++i) {
     float* out = W.Y[i];
     const int ld_out = training ? ld_of(W, i) : ((i % 2 == 0) ? 256 : 320);
     if (i == 4) { in = W.X3E; ld_in = 320; }  // cat([h3, enc]) lives in X3E
+    if (chained) {  // the same operands as nt_x6 below, one table entry per layer
+      chain.l[i] = X6ChainLayer{in, W.WPf + x6_fwd_off(i), Wt(2 * i + 1), out, training ? W.MB[i] : nullptr,
+                                256 * (int64_t)KPAD[i], ld_in, KPAD[i], ld_out, KPAD[i]};
+      in = out;
+      ld_in = ld_out;
+      continue;
+    }
     if (ev) (void)hipEventRecord(ev[2 * i], st);
     if (native)
       TRY(nt<EPI_BIAS_RELU>(in, ld_in, Wt(2 * i), KPAD[i], Wt(2 * i + 1), out, ld_out, nullptr,
@@ -334,6 +350,15 @@ extern "C" int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, floa
     if (ev) (void)hipEventRecord(ev[2 * i + 1], st);
     in = out;
     ld_in = ld_out;
+  }
+  if (chained) {
+    chain.n = 8;
+    for (int i = 0; i < 8; ++i) {
+      if (chain.l[i].K % 64 || chain.l[i].lda % 4 || chain.l[i].ldb % 8) return NERF_E_ARG;
+      // a layer's first 64 input columns are handed over in registers: they must be its predecessor's output
+      if (i > 0 && (chain.l[i].A != chain.l[i - 1].C || chain.l[i].lda != chain.l[i - 1].ldc)) return NERF_E_ARG;
+    }
+    gemm_nt_x6w_chain_kernel<<<(unsigned)(Mp / 256), 512, 0, st>>>(chain);
   }
   // heads + colour MLP + output activations in ONE launch (mlp_fwd_tail.hpp)
   {

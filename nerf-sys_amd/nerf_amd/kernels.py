@@ -162,6 +162,7 @@ def _events_arg(events):
 # fp32 GEMM engine flags (include/nerf_amd.h): 0 = bf16 split products (default), NATIVE_FP32 = fp32 MFMA kernels
 MLP_NATIVE_FP32 = 1
 MLP_NATIVE_DGRAD = 2  # backward only: input-gradient GEMMs on the fp32 MFMA (default: split, small-term accumulators)
+MLP_FWD_LAYERED = 4  # forward only: one GEMM launch per trunk layer (default: one chained launch; bitwise the same)
 
 
 def mlp_fwd(w_packed, x_d, ws, training, out=None, events=None, precision="fp32", bf16_flags=0, fp32_flags=0):
@@ -176,7 +177,7 @@ def mlp_fwd(w_packed, x_d, ws, training, out=None, events=None, precision="fp32"
                                  int(bf16_flags), _events_arg(events), stream()), fn)
         return out
     check(lib().nerf_mlp_fwd_ex(ptr(w_packed), ptr(x_d), M, ptr(out), ptr(ws), ws.numel(), int(training),
-                                int(fp32_flags) & MLP_NATIVE_FP32,  # MLP_NATIVE_DGRAD is a backward-only flag
+                                int(fp32_flags) & ~MLP_NATIVE_DGRAD,  # MLP_NATIVE_DGRAD is a backward-only flag
                                 _events_arg(events), stream()), "nerf_mlp_fwd_ex")
     return out
 
@@ -202,12 +203,13 @@ def mlp_bwd(w_packed, M, d_rgb_sigma, ws, d_w=None, accumulate=False, events=Non
             if not e.cuda_event:
                 e.record()
         check(lib().nerf_mlp_bwd_2s_ex(ptr(w_packed), M, ptr(d_rgb_sigma), ptr(d_w), int(accumulate), ptr(ws),
-                                       ws.numel(), int(fp32_flags), _events_arg(events), stream(),
+                                       ws.numel(), int(fp32_flags) & ~MLP_FWD_LAYERED, _events_arg(events), stream(),
                                        ctypes.c_void_p(wgrad_stream.cuda_stream), _events_arg(sync)),
               "nerf_mlp_bwd_2s_ex")
         return d_w
     check(lib().nerf_mlp_bwd_ex(ptr(w_packed), M, ptr(d_rgb_sigma), ptr(d_w), int(accumulate), ptr(ws), ws.numel(),
-                                int(fp32_flags), _events_arg(events), stream()), "nerf_mlp_bwd_ex")
+                                int(fp32_flags) & ~MLP_FWD_LAYERED,  # MLP_FWD_LAYERED is a forward-only flag
+                                _events_arg(events), stream()), "nerf_mlp_bwd_ex")
     return d_w
 
 

@@ -61,7 +61,10 @@ write = per_kernel(load("WRITE_SIZE"))
 if len(sys.argv) <= 2 and any("_x6" in k[0] for k in fetch):  # fp32 split-product GEMMs (gemm_x6.hpp)
     split_dgrad = any("gemm_nt_x6w_kernel<2," in k[0] for k in fetch)
     CLASSES = {
+        # one launch per layer: only with NERF_MLP_FWD_LAYERED or events (bench.py --full's roofline pass); the plain
+        # bench runs the whole trunk of a net in one gemm_nt_x6w_chain_kernel launch ("fwd_chain": bytes of 8 layers)
         "fwd": ("gemm_nt_x6w_kernel<1,", 0),
+        "fwd_chain": ("gemm_nt_x6w_chain_kernel", 0),
         # default engine: the split input-gradient kernel (small-term accumulators); NERF_MLP_NATIVE_DGRAD: fp32 16x16x4
         "dgrad": ("gemm_nt_x6w_kernel<2," if split_dgrad else "gemm_nt16_kernel<128, 128, 2, 2,", 0),
         "wgrad": ("gemm_wgrad_x6w_kernel", 0),
@@ -71,6 +74,7 @@ for cls, (pat, _) in CLASSES.items():
     # the fine-net trunk launches are the ones with the largest grid of that kernel
     keys = [k for k in fetch if pat in k[0]]
     if not keys:
+        print(f"pmc_parse: no launch of class {cls!r} ({pat}) in this run", file=sys.stderr)
         continue
     gmax = max(k[1] for k in keys)
     kf = [k for k in keys if k[1] == gmax]
