@@ -104,7 +104,9 @@ int nerf_freq_encode(const float* x, int64_t n, int D, int L, int include_input,
 int64_t nerf_mlp_layout(int64_t* table);
 
 /* Workspace (bytes) needed by nerf_mlp_fwd/bwd for M samples.  training!=0 keeps every
- * activation for nerf_mlp_bwd. */
+ * activation for nerf_mlp_bwd, and one [Mp][256] fp32 input-gradient buffer per trunk layer (Mp = M rounded up to
+ * 256): the weight gradient of a layer reads its dZ after the chained input-gradient launch has run.  That is six
+ * buffers more than a two-buffer ping-pong, 4.8 GB at M = 4096 x 192. */
 int64_t nerf_mlp_workspace_bytes(int64_t M, int training);
 
 /* expert(x_d (M,6), params) -> (M,4) [sigmoid rgb, trunc_exp sigma]  (meta_vanilla.py:123-154,
@@ -130,7 +132,7 @@ int nerf_mlp_bwd(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
  * `stream` after the launch that produced its input; `stream` waits for `wgrad_stream` before the final split reduce,
  * so d_w is complete in `stream` order.  sync: 10 caller-created hipEvent_t (hipEventDisableTiming is fine).  The
  * workspace keeps one input-gradient buffer per trunk layer: nerf_mlp_workspace_bytes_2s(M) bytes, filled by a
- * training nerf_mlp_fwd (the forward part of it is nerf_mlp_workspace_bytes(M, 1)'s).  Same kernels, grids and split
+ * training nerf_mlp_fwd (the same layout and size as nerf_mlp_workspace_bytes(M, 1)).  Same kernels, grids and split
  * slabs as nerf_mlp_bwd: d_w is bitwise equal.  The events[4i+0/1] of a weight-gradient GEMM are recorded on
  * wgrad_stream. */
 int64_t nerf_mlp_workspace_bytes_2s(int64_t M);
@@ -160,6 +162,14 @@ int nerf_mlp_bwd_2s(const float* w, int64_t M, const float* d_rgb_sigma, float* 
  * event pair brackets one layer's launch: per-layer timings are always those of a layer launched alone.  No effect
  * with NERF_MLP_NATIVE_FP32.  nerf_mlp_bwd_ex does not know this bit (NERF_E_ENUM). */
 #define NERF_MLP_FWD_LAYERED 4
+/* NERF_MLP_BWD_LAYERED (backward, with the split engine): one input-gradient launch per trunk layer, each followed by
+ * the layer's weight gradient.  By default nerf_mlp_bwd runs the seven trunk input gradients in ONE chained launch
+ * (a 256-row tile per workgroup, both 128-column tiles of every layer) right after the head backward, and the weight
+ * gradients after it.  The chained launch runs the per-layer kernel's tile code, so every dZ_i and d_w are bitwise the
+ * layered form's (tests/test_gpu_bwd_chain.py).  The layered form also runs when events != NULL (an event pair brackets
+ * one launch), with a weight-gradient stream (nerf_mlp_bwd_2s), with NERF_MLP_NATIVE_DGRAD and with
+ * NERF_MLP_NATIVE_FP32.  nerf_mlp_fwd_ex does not know this bit (NERF_E_ENUM). */
+#define NERF_MLP_BWD_LAYERED 8
 int nerf_mlp_fwd_ex(const float* w, const float* x_d, int64_t M, float* rgb_sigma, void* ws, int64_t ws_bytes,
                     int training, int flags, hipEvent_t* events, hipStream_t stream);
 int nerf_mlp_bwd_ex(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w, int accumulate, void* ws,

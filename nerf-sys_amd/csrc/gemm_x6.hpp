@@ -127,13 +127,17 @@ __device__ __forceinline__ void x6_swap32(float& a, float& b) {
 // 8 q + 4 lh + e of block b; the A fragment of k-step ks of slab b wants lane (r, h) to hold k = 16 ks + 8 h + 0 .. 7.
 // For q0 = 2 ks, v_permlane32_swap of (q0, e) with (q0 + 1, e) swaps the first register's upper lanes with the second's
 // lower lanes: the first then holds k = 16 ks + 8 h + e and the second k = 16 ks + 8 h + 4 + e on both lane halves.
-template <int TM, int TN, int EPI, bool HAND = false>
+// PREW (EPI_MASK, TM = 1): the mask words of the lane's row come in pw[TN] (x6w_tile loads them under the last slab), so
+// the epilogue issues no global load: a load here sits behind the previous block's stores in the in-order counter.
+template <int TM, int TN, int EPI, bool HAND = false, bool PREW = false>
 __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int64_t mw, int n0, int lane,
                                                 const float* __restrict__ bias, float* __restrict__ C, int ldc,
                                                 const uint32_t* __restrict__ mbits, int ldmb,
                                                 uint32_t* __restrict__ mbits_out, float* E,
-                                                float4 (*ho)[1][2][2] = nullptr, const float* bias_lds = nullptr) {
+                                                float4 (*ho)[1][2][2] = nullptr, const float* bias_lds = nullptr,
+                                                const uint32_t* pw = nullptr) {
   static_assert(!HAND || (TM == 1 && TN >= 2 && EPI == EPI_BIAS_RELU), "hand-off: the forward tile");
+  static_assert(!PREW || (TM == 1 && EPI == EPI_MASK), "preloaded mask words: the input-gradient tile");
   const int li = lane & 31, lh = lane >> 5;
   const int rr = lane >> 3, cc = 4 * (lane & 7);  // read-back: row rr + 8 i, columns cc .. cc + 3
 #pragma unroll
@@ -156,7 +160,11 @@ __device__ __forceinline__ void x6_epilogue_lds(nerf_f32x16 (&acc)[TM][TN], int6
     for (int a = 0; a < TM; ++a) {
       const int64_t m = mw + a * 32 + li;
       uint32_t word = 0;
-      if (EPI == EPI_MASK) word = mbits[m * ldmb + g];
+      if constexpr (PREW) {
+        word = pw[b];
+      } else if (EPI == EPI_MASK) {
+        word = mbits[m * ldmb + g];
+      }
       float hv[4][4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -236,6 +244,15 @@ constexpr int x6w_smem_elems() { return 2 * 3 * (32 * TN) * 32; }
 // one finds its slabs 0 and 1 in ra[0] / ra[1] (the previous layer's epilogue left them there) and its slab-0 weights
 // already in buffer 0, and skips the prologue.  nBp / nldb / nbplane (CH = 1): the next layer's weight planes, nBp ==
 // nullptr after the last layer.
+// CH = 2: once per body by gemm_nt_x6w_dgrad_chain_kernel (the input-gradient tile, NKC = 8).  smem then has NW
+// X6E_WAVE_FLOATS floats behind the weight buffers for the epilogue tiles.  After the last barrier of its slab loop
+// the body issues the NEXT body's slab-0 / slab-1 activation loads (nA, the same pitch lda) into ra[0] / ra[1], and its
+// last slab fetches the next body's slab-0 weights (nBp / nldb / nbplane, rows nn0 ..) into buffer 0; every body but
+// the `first` skips the prologue.  After the last body the caller passes the body's own operands again (dead loads of
+// valid addresses keep the instruction stream free of a branch).
+// The row's four mask words are then loaded (one 16-B load) at the start of the last slab, whose closing vmcnt(0) covers
+// them, and the epilogue issues no global load (x6_epilogue_lds PREW).  The per-layer launch keeps its own stream: the
+// preload alone measured 0.060 ms per step there, 2.3 x the run-to-run spread (profiles/bwd_chain_ab.txt).
 template <int EPI, bool BIGSMALL, int NKC, int TN, int CH = 0>
 __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, const nerf_bf16* __restrict__ Bp,
                                          int ldb, int64_t bplane, const float* __restrict__ bias,
@@ -243,8 +260,12 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
                                          uint32_t* __restrict__ mbits_out, int K, int64_t m0, int n0,
                                          nerf_bf16* smem, float4 (&ra)[NKC > 0 ? 3 : 2][1][2][2],
                                          const nerf_bf16* nBp = nullptr, int nldb = 0, int64_t nbplane = 0,
-                                         bool first = true) {
-  static_assert(CH == 0 || (NKC == 0 && EPI == EPI_BIAS_RELU), "chained: the forward tile");
+                                         bool first = true, const float* nA = nullptr, int nn0 = 0) {
+  static_assert(CH != 1 || (NKC == 0 && EPI == EPI_BIAS_RELU), "chained: the forward tile");
+  static_assert(CH != 2 || (NKC > 0 && EPI == EPI_MASK), "chained: the input-gradient tile");
+  constexpr bool PF = CH == 2;    // the body hands its successor slabs 0 / 1 and the slab-0 weights ...
+  constexpr bool PREW = CH == 2;  // ... and preloads its mask words
+  static_assert(!PREW || TN == 4, "preloaded mask words: one 16-B load per row");
   constexpr int BK = 32, NW = 8, TM = 1;          // slab depth, waves, 32-row blocks per wave
   constexpr int WTM = 32 * TM, BM = WTM * NW, BN = 32 * TN;
   constexpr int KS = BK / 16;                     // MFMA k-steps per slab
@@ -260,8 +281,10 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
   static_assert(2 * 3 * PL >= NW * X6E_WAVE_FLOATS * 2, "epilogue tiles");
   // chained: buffer 0 receives the next layer's slab 0 during the last slab, so the tiles take buffer 1 alone
   // ... followed by one copy of the layer's bias row (BN floats) per wave
-  static_assert(CH == 0 || 3 * PL >= NW * (X6E_WAVE_FLOATS + BN) * 2, "epilogue tiles and bias rows in buffer 1");
-  static_assert(CH == 0 || BN == 256, "bias row: one float4 per lane");
+  static_assert(CH != 1 || 3 * PL >= NW * (X6E_WAVE_FLOATS + BN) * 2, "epilogue tiles and bias rows in buffer 1");
+  static_assert(CH != 1 || BN == 256, "bias row: one float4 per lane");
+  // CH = 2: buffer 0 holds the next body's slab 0 during the epilogue and one 24-KiB buffer is smaller than the 36 KiB
+  // of tiles, so they live behind the two buffers
   static_assert(2 * 3 * PL == x6w_smem_elems<TN>(), "weight buffers");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -288,13 +311,14 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t gofs = (uint32_t)((((lane >> 2) * ldb) + 8 * ((lane & 3) ^ ((lane >> 4) & 3))) * 2);
   const uint32_t ngofs = (uint32_t)((((lane >> 2) * nldb) + 8 * ((lane & 3) ^ ((lane >> 4) & 3))) * 2);
-  const nerf_bf16* nBb = nBp + (int64_t)n0 * nldb;
+  const nerf_bf16* nBb = nBp + (int64_t)(CH == 2 ? nn0 : n0) * nldb;
   const uint32_t smem_u32 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
-#define X6W_ALOAD(set_, k0_)                                                                              \
+#define X6W_ALOAD(set_, k0_) X6W_ALOAD_SRC(At, set_, k0_)
+#define X6W_ALOAD_SRC(At_, set_, k0_)                                                                     \
   _Pragma("unroll") for (int a = 0; a < TM; ++a)                                                         \
     _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                    \
       _Pragma("unroll") for (int hf = 0; hf < 2; ++hf)                                                   \
-        ra[set_][a][ks][hf] = *reinterpret_cast<const float4*>(At + aoff[a] + (k0_) + 16 * ks + 4 * hf);
+        ra[set_][a][ks][hf] = *reinterpret_cast<const float4*>((At_) + aoff[a] + (k0_) + 16 * ks + 4 * hf);
   // B fragments are read per pair of column blocks (2 x 3 fragments live).  Measured and not kept
   // (profiles/r04/x6_bfrag_ab.txt): one block at a time (fwd 0.603 -> 0.612 ms), with the next block read under the
   // current block's MFMAs (0.613-0.619); the two 4-wave halves staggered by one barrier (ping-pong): fwd 0.58 -> 0.64,
@@ -336,7 +360,8 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
 
   const int nk = A3 ? NKC : K / BK;
   float4 bz = make_float4(0.f, 0.f, 0.f, 0.f);  // chained: this lane's four values of the bias row, for the epilogue
-  if constexpr (CH != 0) bz = *reinterpret_cast<const float4*>(bias + n0 + 4 * lane);
+  if constexpr (CH == 1) bz = *reinterpret_cast<const float4*>(bias + n0 + 4 * lane);
+  uint4 pw4 = make_uint4(0u, 0u, 0u, 0u);   // PREW: the four mask words of row m0 + 32 wave + li
   if (CH == 0 || first) {
     X6W_ALOAD(0, 0);
     X6W_ALOAD(1, (nk > 1 ? 1 : 0) * BK);
@@ -365,7 +390,7 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
           // after after_split's loads, the old and new values of a set then interfere, and the allocator gives the loads
           // other registers and copies them at the end of the round — behind a vmcnt(0) that drains the loads in flight
           // (seen in the chained kernel: 8 v_mov_b64 and the drain per round)
-          if constexpr (CH != 0) {
+          if constexpr (CH == 1) {
             if (ks == KS - 1) {
 #pragma unroll
               for (int a = 0; a < TM; ++a) asm volatile("" ::"v"(af[a][0]), "v"(af[a][1]), "v"(af[a][2]) : "memory");
@@ -406,7 +431,17 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
 #pragma unroll
     for (int kt = 0; kt < NKC; ++kt) {
       const int j = kt % 3;
-      X6W_BLOAD((kt + 1 < NKC ? kt + 1 : kt) * BK, (kt + 1) & 1);
+      if (PF && kt == NKC - 1) {
+        // the last slab would fetch its own weights again: it fetches the next body's slab 0 instead, which lands in
+        // buffer 0 behind this slab's vmcnt(0) and barrier like any other slab
+        X6W_BLOAD_SRC(nBb, nldb, nbplane, ngofs, 0, (kt + 1) & 1);
+      } else {
+        X6W_BLOAD((kt + 1 < NKC ? kt + 1 : kt) * BK, (kt + 1) & 1);
+      }
+      if constexpr (PREW) {
+        if (kt == NKC - 1)
+          pw4 = *reinterpret_cast<const uint4*>(mbits + (m0 + wave * WTM + li) * ldmb + (n0 >> 5));
+      }
       // set (kt + 2) % 3 was consumed by slab kt - 1; the last two slabs load nothing (a dead load would be deleted by the
       // compiler and leave the counted weight wait short), so their weight wait drains the queue
       if (kt + 2 < NKC) X6W_ALOAD((kt + 2) % 3, (kt + 2) * BK);
@@ -418,6 +453,16 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();
+    }
+    if constexpr (PF) {
+      // sets 0 and 1 are dead (slabs 6 and 7 are split) and nothing is in flight: the next body's slabs 0 and 1, issued
+      // before the epilogue's first store so that they are older than every store in the in-order counter.  Columns
+      // 0 .. 63 of the next A were stored either by another launch or by the nt = 0 epilogue of this layer, which the
+      // vmcnt(0) of the slab loop above has drained.  Pinned: hipcc may not sink them below the epilogue.
+      const float* nAt = nA + (m0 + wave * WTM) * lda;
+      X6W_ALOAD_SRC(nAt, 0, 0);
+      X6W_ALOAD_SRC(nAt, 1, BK);
+      asm volatile("" ::: "memory");
     }
   } else {
     for (int kt0 = 0; kt0 < nk; kt0 += 2) {
@@ -452,6 +497,7 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
     __syncthreads();
   }
 #undef X6W_ALOAD
+#undef X6W_ALOAD_SRC
 #undef X6W_BLOAD
 #undef X6W_BLOAD_SRC
 #undef X6W_BWAIT
@@ -465,13 +511,15 @@ __device__ __forceinline__ void x6w_tile(const float* __restrict__ A, int lda, c
   // the loop's last barrier freed the weight images: every wave stages its 32 x 32 blocks through a private LDS
   // tile and stores whole 128-B row lines (8 lanes per row; x6_epilogue_lds)
   float* Eb = nullptr;  // chained: this wave's copy of the bias row, behind the eight tiles in buffer 1
-  if constexpr (CH != 0) {
+  if constexpr (CH == 1) {
     Eb = reinterpret_cast<float*>(smem + 3 * PL) + NW * X6E_WAVE_FLOATS + wave * BN - n0;
     *reinterpret_cast<float4*>(Eb + n0 + 4 * lane) = bz;
   }
-  x6_epilogue_lds<TM, TN, EPI, CH != 0>(acc, m0 + wave * WTM, n0, lane, bias, C, ldc, mbits, ldmb, mbits_out,
-                                        reinterpret_cast<float*>(smem + (CH != 0 ? 3 * PL : 0)) + wave * X6E_WAVE_FLOATS,
-                                        CH != 0 ? &ra[0] : nullptr, Eb);
+  const uint32_t pw[4] = {pw4.x, pw4.y, pw4.z, pw4.w};
+  x6_epilogue_lds<TM, TN, EPI, CH == 1, PREW>(
+      acc, m0 + wave * WTM, n0, lane, bias, C, ldc, mbits, ldmb, mbits_out,
+      reinterpret_cast<float*>(smem + (CH == 1 ? 3 * PL : (CH == 2 ? 2 * 3 * PL : 0))) + wave * X6E_WAVE_FLOATS,
+      CH == 1 ? &ra[0] : nullptr, Eb, pw);
 }
 
 template <int EPI, bool BIGSMALL, int NKC, int TN>
@@ -550,6 +598,58 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_x6w_chain_kernel(const X6Chain
     X6_CHAIN_NEXT()
   }
 #undef X6_CHAIN_NEXT
+}
+
+// ------------------------------------------------------------------------------------------ chained input gradient
+// The trunk input gradients are row-local too once ONE workgroup does both 128-column tiles of a 256-row tile: in the
+// input-gradient tile wave w loads rows m0 + 32 w .. + 31 of dZ_i and stores the same rows of dZ_{i-1}; after (layer i,
+// columns 0 .. 127) and (layer i, columns 128 .. 255) it has written every column of its rows, which are exactly its A
+// operand of layer i - 1.  One launch therefore runs the 2 n bodies of a row tile — x6w_tile<EPI_MASK, true, 8, 4> in
+// chain mode CH = 2, the per-layer launch's slab loop and MFMA sequence on every accumulator, so every stored value is
+// bitwise the per-layer launches' (tests/test_gpu_bwd_chain.py) — from a by-value table it only reads.
+// Between two bodies, as in the forward chain: a wavefront-scope release / acquire fence pair (the wave's own stores
+// before its own later loads) and one workgroup barrier (no LDS region is refilled before every wave has finished
+// reading it, and every wave's part of the prefetched slab-0 weights has landed).  No flags, no polling, no atomics,
+// nothing between workgroups: a tile touches only its own rows of every buffer.
+// Each body hands its successor what a launch would fetch in its prologue (x6w_tile CH = 2): the next slab-0 weights
+// arrive during the last slab, and the next slab-0 / slab-1 activation loads are issued before the epilogue's first
+// store.  The epilogue tiles (36 KiB) have LDS of their own behind the two 24-KiB weight buffers: 84 KiB, one
+// workgroup per CU as before (registers).  Against the fourteen launches: 16.578 -> 16.301 ms per step; chaining
+// alone, with every body's own prologue, was not faster (profiles/bwd_chain_ab.txt).  Resources
+// (-Rpass-analysis=kernel-resource-usage): 248 VGPRs, 72 SGPRs, no scratch, 84 KiB LDS, two waves per SIMD.
+// l[k] is the k-th layer IN EXECUTION ORDER (trunk.7's input gradient first): C of l[k] must be A of l[k + 1], and
+// lda / ldb / bplane are the same for every entry (the host checks both).
+struct X6DgradLayer {
+  const float* A;         // dZ_i, row pitch lda
+  const nerf_bf16* Bp;    // transposed weight piece planes [3][256][ldb], plane stride bplane
+  float* C;               // dZ_{i-1}, row pitch ldc
+  const uint32_t* mbits;  // ReLU mask words of trunk.(i-1)'s output [M][ldmb]
+  int64_t bplane;
+  int lda, ldb, ldc, ldmb;
+};
+constexpr int X6_DGRAD_CHAIN_MAX = 7;
+struct X6DgradChain {
+  X6DgradLayer l[X6_DGRAD_CHAIN_MAX];
+  int n;
+};
+constexpr int x6w_dgrad_chain_smem_elems() { return x6w_smem_elems<4>() + 8 * X6E_WAVE_FLOATS * 2; }
+__global__ __launch_bounds__(512, 1) void gemm_nt_x6w_dgrad_chain_kernel(const X6DgradChain ch) {
+  __shared__ __attribute__((aligned(16))) nerf_bf16 smem[x6w_dgrad_chain_smem_elems()];
+  const int64_t m0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 256;
+  float4 ra[3][1][2][2];
+  const int nb = 2 * ch.n;
+#pragma unroll 1
+  for (int b = 0; b < nb; ++b) {
+    const int bn = b + 1 < nb ? b + 1 : b;  // after the last body: its own operands again
+    const X6DgradLayer& L = ch.l[b >> 1];
+    const X6DgradLayer& N = ch.l[bn >> 1];
+    x6w_tile<EPI_MASK, true, 8, 4, 2>(L.A, L.lda, L.Bp, L.ldb, L.bplane, nullptr, L.C, L.ldc, L.mbits, L.ldmb, nullptr,
+                                      256, m0, 128 * (b & 1), smem, ra, N.Bp, N.ldb, N.bplane, b == 0, N.A,
+                                      128 * (bn & 1));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __syncthreads();
+  }
 }
 
 // ------------------------------------------------------------------------------------------ gemm_wgrad_x6

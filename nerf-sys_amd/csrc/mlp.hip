@@ -12,13 +12,21 @@
 //   X3E [Mp][320] : cols 0..255 = trunk.3 output, cols 256..318 = xyz encoding, col 319 = 0
 //                   (so trunk.4 reads cat([h, enc]) with K = 320 and no copy; trunk.0 reads cols 256..319)
 //   Y0..Y2, Y4..Y7 [Mp][256], HO [Mp][4] (colour pre-activations 0..2, sigma_raw), CIN [Mp][64] (geo | dir-enc |
-//   0), C0 [Mp][128].  Backward adds dA/dB [Mp][256], dO16 [Mp][16] (from the fused colour-branch backward),
-//   transposed trunk weights, and S split-M partial slabs of the packed gradient.
+//   0), C0 [Mp][128].  Backward adds dZ0..dZ7 [Mp][256] (the input gradient of every trunk layer in a buffer of its
+//   own), dO16 [Mp][16] (from the fused colour-branch backward), transposed trunk weights, and S split-M partial slabs
+//   of the packed gradient.
 //
 // Forward launches (nerf_mlp_fwd_ex), split engine: pe_xyz, x6_planes (this call's weights as bf16 piece planes),
 // gemm_nt_x6w_chain (trunk.0 .. trunk.7 in one launch, a 256-row tile per workgroup), fwd_tail.  With
 // NERF_MLP_FWD_LAYERED or with events the trunk is eight gemm_nt_x6w launches (the chain's bitwise reference, and
 // what the per-layer event pairs time); with NERF_MLP_NATIVE_FP32: pe_xyz, eight gemm_nt16, fwd_tail.
+//
+// Backward launches (nerf_mlp_bwd_ex), split engine, one stream: x6_planes (the transposed weights as piece planes),
+// color_bwd, head_bwd (writes dZ7), gemm_nt_x6w_dgrad_chain (dZ6 .. dZ0 in one launch, a 256-row tile per workgroup),
+// the weight gradients of trunk.7 .. trunk.0 (eight gemm_wgrad_x6w and the two narrow gemm_wgrad_x6 of trunk.4 and
+// trunk.0), reduce_splits2.  With NERF_MLP_BWD_LAYERED, with events, with a weight-gradient stream or with
+// NERF_MLP_NATIVE_DGRAD the input gradients are seven launches of two column tiles each (gemm_nt_x6w, or gemm_nt16),
+// each behind its layer's weight gradient: the chain's bitwise reference, and what the per-layer event pairs time.
 #include "gemm.hpp"
 #include "gemm_x6.hpp"
 #include "mlp_common.hpp"
@@ -33,8 +41,9 @@ struct WS {
   float *X3E, *Y[8], *HO, *CIN, *C0;
   uint32_t* MB[8];  // ReLU bitmasks of the trunk outputs [Mp][8] (colour layer 0 re-derives its mask from C0 > 0)
   // backward
-  float *dA, *dB, *dO16, *WT, *partial, *partial2;
-  float* dZ[8];  // two-stream backward (training == 2): one input-gradient buffer per trunk layer (dZ_i of trunk.i)
+  float *dO16, *WT, *partial, *partial2;
+  float* dZ[8];  // one input-gradient buffer per trunk layer (dZ_i of trunk.i): the weight gradient of layer i reads
+                 // dZ_i after the whole input-gradient chain has run (one stream) or while it runs ahead (two streams)
   nerf_bf16* WPf;  // bf16 piece planes of the trunk weights (split GEMMs): layer i at x6_fwd_off(i), [3][256][KPAD_i]
   nerf_bf16* WPb;  // ... of the transposed trunk weights (input gradients): layer i >= 1 at 3 * 65536 * (i - 1)
   int S;
@@ -77,14 +86,8 @@ WS carve(void* base, int64_t M, int training) {
   w.C0 = take(Mp * 128);
   if (training) {
     for (int i = 0; i < 8; ++i) w.MB[i] = reinterpret_cast<uint32_t*>(take(Mp * 8));
-    if (training == 2) {  // the weight-gradient stream reads dZ_i while the input-gradient chain runs ahead
-      for (int i = 0; i < 8; ++i) w.dZ[i] = take(Mp * 256);
-      w.dA = w.dZ[7];
-      w.dB = w.dZ[6];
-    } else {
-      w.dA = take(Mp * 256);
-      w.dB = take(Mp * 256);
-    }
+    // one training layout for the one-stream (1) and the two-stream (2) backward
+    for (int i = 0; i < 8; ++i) w.dZ[i] = take(Mp * 256);
     w.dO16 = take(Mp * 16);  // [Mp][16]: the head-output gradient, written by color_bwd, read by head_bwd
     w.WT = take(WT_FLOATS);
     w.WPb = reinterpret_cast<nerf_bf16*>(take(X6_BWD_BF16 / 2));
@@ -399,7 +402,7 @@ int mlp_bwd_impl(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
                  int64_t ws_bytes, int flags, hipEvent_t* ev, hipStream_t st, hipStream_t stw, hipEvent_t* sync) {
   NERF_CHECK_ARG(w && d_w && ws && M >= 0 && (M == 0 || d_rgb_sigma));
   NERF_CHECK_ARG(!stw || sync);
-  if (flags & ~(NERF_MLP_NATIVE_FP32 | NERF_MLP_NATIVE_DGRAD)) return NERF_E_ENUM;
+  if (flags & ~(NERF_MLP_NATIVE_FP32 | NERF_MLP_NATIVE_DGRAD | NERF_MLP_BWD_LAYERED)) return NERF_E_ENUM;
   const bool native = flags & NERF_MLP_NATIVE_FP32;
   // input gradients: split products with the small terms in their own accumulators (gemm_nt_x6w BIGSMALL) unless
   // NERF_MLP_NATIVE_DGRAD keeps them on the fp32 MFMA
@@ -407,6 +410,10 @@ int mlp_bwd_impl(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
   if (!nerf_aligned16(w) || !nerf_aligned16(ws) || !nerf_aligned16(d_w) || !nerf_aligned16(d_rgb_sigma))
     return NERF_E_ALIGN;
   const bool two = stw != nullptr;
+  // the seven split input gradients in ONE launch (gemm_nt_x6w_dgrad_chain_kernel), followed by the weight gradients,
+  // unless the caller asks for the per-layer launches, for their events (an event pair brackets one launch) or for a
+  // weight-gradient stream (whose launches trail the per-layer input gradients)
+  const bool chained = split_dgrad && !ev && !two && !(flags & NERF_MLP_BWD_LAYERED);
   const WS W = carve(ws, M, two ? 2 : 1);
   if (ws_bytes < W.bytes) return NERF_E_WORKSPACE;
   hipStream_t sw = two ? stw : st;  // the weight-gradient stream
@@ -445,20 +452,38 @@ int mlp_bwd_impl(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
 
   // colour branch + head activations in one kernel: dO16 and the colour weight / bias slabs (TAIL_NQ workgroups per
   // split; the colour sums of parts 1.. go to W.partial2 and are added by the final reduce)
-  float* dcur = W.dA;
-  float* dnext = W.dB;
   // events 2/3 (layer 0 has no input gradient) bracket the backward tail (colour branch + heads -> dZ7)
   if (ev) (void)hipEventRecord(ev[2], st);
   // colour branch -> dO16 [Mp][16]; then ONE pass over Y7 for dZ7 and the head weight / bias sums (mlp_tail.hpp)
   color_bwd_kernel<float, float><<<TAIL_NQ * W.S, 256, 0, st>>>(d_rgb_sigma, W.HO, W.C0, W.CIN, Wt(18), Wt(20), W.dO16,
                                                           W.partial, L.total, L.off[18], L.off[19], L.off[20], L.off[21],
                                                           W.rps, M, Mp, W.partial2, L.total - P2BASE, P2BASE, 16);
-  head_bwd_kernel<<<TAIL_NQ * W.S, 256, 0, st>>>(W.dO16, W.Y[7], Wt(16), dcur, W.partial, L.total, W.partial2,
+  head_bwd_kernel<<<TAIL_NQ * W.S, 256, 0, st>>>(W.dO16, W.Y[7], Wt(16), W.dZ[7], W.partial, L.total, W.partial2,
                                            L.total - P2BASE, P2BASE, L.off[16], L.off[17], W.rps, Mp);
   if (ev) (void)hipEventRecord(ev[3], st);
   TRY(handoff(1));  // dZ7 and the head / colour slabs are complete
+  if (chained) {  // the same operands as the nt_x6 launches below, one table entry per layer, trunk.7 first
+    X6DgradChain chain{};
+    chain.n = 7;
+    for (int i = 7; i >= 1; --i)
+      chain.l[7 - i] = X6DgradLayer{W.dZ[i], W.WPb + 3 * 65536 * (int64_t)(i - 1), W.dZ[i - 1], W.MB[i - 1], 65536,
+                                    256, 256, 256, 8};
+    for (int k = 0; k < chain.n; ++k) {
+      const X6DgradLayer& E = chain.l[k];
+      // what nt_x6<EPI_MASK> checks, the 16-B accesses of the tile, and one pitch for every entry (a body prefetches
+      // its successor's operands with its own)
+      if (E.lda % 4 || E.ldb % 8 || E.ldc % 4 || E.ldmb % 4 || E.lda < 256 || E.ldc < 256 || E.ldmb < 8) return NERF_E_ARG;
+      if (E.lda != chain.l[0].lda || E.ldb != chain.l[0].ldb || E.bplane != chain.l[0].bplane) return NERF_E_ARG;
+      if (!nerf_aligned16(E.A) || !nerf_aligned16(E.Bp) || !nerf_aligned16(E.C) || !nerf_aligned16(E.mbits))
+        return NERF_E_ALIGN;
+      // a layer reads the rows its predecessor stored in the same workgroup
+      if (k > 0 && (E.A != chain.l[k - 1].C || E.lda != chain.l[k - 1].ldc)) return NERF_E_ARG;
+    }
+    gemm_nt_x6w_dgrad_chain_kernel<<<(unsigned)(Mp / 256), 512, 0, st>>>(chain);
+  }
   // trunk
   for (int i = 7; i >= 0; --i) {
+    float* dcur = W.dZ[i];
     const float* X = (i == 0) ? W.X3E + 256 : (i == 4 ? W.X3E : W.Y[i - 1]);
     const int ldx = (i == 0 || i == 4) ? 320 : ld_of(W, i - 1);
     if (two && i < 7) TRY(handoff(8 - i));  // dZ_i, written by the trunk.(i+1) dgrad: sync[8 - i]
@@ -468,8 +493,8 @@ int mlp_bwd_impl(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
     else
       TRY(wgrad_x6(dcur, 256, X, ldx, 2 * i, W, 256, KPAD[i], sw));
     if (ev) (void)hipEventRecord(ev[4 * i + 1], sw);
-    if (i > 0) {
-      if (two) dnext = W.dZ[i - 1];  // never the buffer a trailing weight gradient still reads
+    if (i > 0 && !chained) {
+      float* dnext = W.dZ[i - 1];  // never a buffer that a later (or trailing) weight gradient still reads
       if (ev) (void)hipEventRecord(ev[4 * i + 2], st);
       if (!split_dgrad)
         TRY(nt<EPI_MASK>(dcur, 256, WTi[i], 256, nullptr, dnext, 256, W.MB[i - 1], nullptr, Mp, 256, 256, st));
@@ -477,7 +502,6 @@ int mlp_bwd_impl(const float* w, int64_t M, const float* d_rgb_sigma, float* d_w
         TRY(nt_x6<EPI_MASK>(dcur, 256, W.WPb + 3 * 65536 * (int64_t)(i - 1), 256, 65536, nullptr, dnext, 256,
                             W.MB[i - 1], nullptr, Mp, 256, 256, st));
       if (ev) (void)hipEventRecord(ev[4 * i + 3], st);
-      float* t = dcur; dcur = dnext; dnext = t;
     }
   }
   if (two) {  // join: the split reduce reads every weight-gradient slab

@@ -163,6 +163,7 @@ def _events_arg(events):
 MLP_NATIVE_FP32 = 1
 MLP_NATIVE_DGRAD = 2  # backward only: input-gradient GEMMs on the fp32 MFMA (default: split, small-term accumulators)
 MLP_FWD_LAYERED = 4  # forward only: one GEMM launch per trunk layer (default: one chained launch; bitwise the same)
+MLP_BWD_LAYERED = 8  # backward only: one input-gradient launch per trunk layer (default: one chained launch; bitwise the same)
 
 
 def mlp_fwd(w_packed, x_d, ws, training, out=None, events=None, precision="fp32", bf16_flags=0, fp32_flags=0):

@@ -67,6 +67,9 @@ if len(sys.argv) <= 2 and any("_x6" in k[0] for k in fetch):  # fp32 split-produ
         "fwd_chain": ("gemm_nt_x6w_chain_kernel", 0),
         # default engine: the split input-gradient kernel (small-term accumulators); NERF_MLP_NATIVE_DGRAD: fp32 16x16x4
         "dgrad": ("gemm_nt_x6w_kernel<2," if split_dgrad else "gemm_nt16_kernel<128, 128, 2, 2,", 0),
+        # the plain bench runs the seven input gradients of a net in one gemm_nt_x6w_dgrad_chain_kernel launch
+        # ("dgrad_chain": bytes of 7 layers); the per-layer class above appears with NERF_MLP_BWD_LAYERED or events
+        "dgrad_chain": ("gemm_nt_x6w_dgrad_chain_kernel", 0),
         "wgrad": ("gemm_wgrad_x6w_kernel", 0),
     }
 res, detail = {}, {}
