@@ -233,6 +233,21 @@ int nerf_composite_bwd(const float* rgb_sigma, const float* t, const float* bg, 
                        float sigma_scale, const float* g_rgb, const float* g_depth, const float* g_acc,
                        const float* g_weights, float* d_rgb_sigma, hipStream_t stream);
 
+/* ------------------------------------------------------------------ image metrics */
+
+/* runtime_evaluate's full-image metrics (pipelines/online_stage/runtime_adapt.py:150-158): color_space_transformer
+ * (nerfs/color_space.py:22-66) on both images, then the MSE of PSNR and pytorch_msssim.ssim(data_range=1) per channel
+ * (11-tap Gaussian window, sigma 1.5, valid convolution, C1 = 1e-4, C2 = 9e-4, mean of the unclamped map).
+ * pred (n_img,H,W,3) is the linear render; the ground truth is 8-bit sRGB (gt_u8, converted as v / 255) or the same
+ * as floats (gt_f32): exactly one of the two is non-NULL.  color_space as nerf_composite_fwd.  H, W >= 11.
+ * out (n_img,4) = mse, ssim_r, ssim_g, ssim_b.  ws: nerf_image_metrics_workspace_bytes bytes, 16-byte aligned
+ * (per-tile partial sums; a second launch adds them in a fixed order in double, so equal inputs give equal bits).
+ * n_img == 0 is an empty call.  nerf_image_metrics_tile reports the SSIM-map pixels one workgroup covers. */
+int nerf_image_metrics_tile(int* tile_h, int* tile_w);
+int64_t nerf_image_metrics_workspace_bytes(int64_t n_img, int H, int W);
+int nerf_image_metrics(const float* pred, const float* gt_f32, const uint8_t* gt_u8, int64_t n_img, int H, int W,
+                       int color_space, void* ws, int64_t ws_bytes, float* out, hipStream_t stream);
+
 /* ------------------------------------------------------------------ optimiser */
 
 /* Per-block partial sums of squares of g (n) into partials[256] (first pass of

@@ -48,6 +48,16 @@ __device__ __forceinline__ float nerf_uniform(uint64_t seed, uint64_t a, uint64_
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
+// ---------------------------------------------------------------- colour transfer (nerfs/color_space.py:4-19)
+// The sRGB transfer functions of the loss head and of the image metrics; x is already clamped to [0,1].
+// linear_to_srgb is also an expression macro: the loss head tests the knee once for the value and its slope, and
+// only the expression written in place lets the compiler keep that one branch (an inlined call compiles to two).
+#define NERF_LINEAR_TO_SRGB(x) ((x) <= 0.0031308f ? 12.92f * (x) : 1.055f * powf((x), 1.0f / 2.4f) - 0.055f)
+__device__ __forceinline__ float nerf_srgb_to_linear(float x) {
+  return x <= 0.04045f ? x / 12.92f : powf((x + 0.055f) / 1.055f, 2.4f);
+}
+__device__ __forceinline__ float nerf_linear_to_srgb(float x) { return NERF_LINEAR_TO_SRGB(x); }
+
 // ---------------------------------------------------------------- wave scans (64 lanes)
 __device__ __forceinline__ int nerf_lane() { return (int)(threadIdx.x & 63); }
 

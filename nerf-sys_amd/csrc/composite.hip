@@ -78,10 +78,6 @@ __device__ __forceinline__ void transmittance(const SampleState (&st)[SPL], floa
   }
 }
 
-__device__ __forceinline__ float srgb_to_linear(float x) {
-  return x <= 0.04045f ? x / 12.92f : powf((x + 0.055f) / 1.055f, 2.4f);
-}
-
 // The loss head's sum: one float atomic per workgroup of FWD_RAYS rays (the per-ray partials meet in LDS first).  With
 // one atomic per ray the 4096 same-address atomics of a C2 batch serialised at the L2: 56-61 us per fine / coarse
 // launch on MI355X (profiles/r03/prof_fp32_summary.txt) for ~15 MB of data.
@@ -135,10 +131,10 @@ __global__ __launch_bounds__(64 * FWD_RAYS) void composite_fwd_kernel(const floa
       if (cs == 0) {  // linear: compare clamp(pred) with clamp(srgb_to_linear(gt))
         pp = fminf(fmaxf(p, 0.f), 1.f);
         dp = (p >= 0.f && p <= 1.f) ? 1.f : 0.f;
-        g = fminf(fmaxf(srgb_to_linear(g), 0.f), 1.f);
+        g = fminf(fmaxf(nerf_srgb_to_linear(g), 0.f), 1.f);
       } else if (cs == 1) {  // srgb: compare clamp(linear_to_srgb(pred)) with gt
         const float xc = fminf(fmaxf(p, 0.f), 1.f);
-        const float y = xc <= 0.0031308f ? 12.92f * xc : 1.055f * powf(xc, 1.0f / 2.4f) - 0.055f;
+        const float y = NERF_LINEAR_TO_SRGB(xc);
         const float dy = xc <= 0.0031308f ? 12.92f : (1.055f / 2.4f) * powf(xc, 1.0f / 2.4f - 1.0f);
         pp = fminf(fmaxf(y, 0.f), 1.f);
         dp = ((y >= 0.f && y <= 1.f) ? 1.f : 0.f) * ((p >= 0.f && p <= 1.f) ? dy : 0.f);

@@ -80,6 +80,9 @@ def lib():
             "nerf_mlp_bwd_f16": [P, I64, P, P, I, P, I64, I, P, P],
             "nerf_composite_fwd": [P, P, P, I64, I, F, P, P, P, P, P, I, F, P, P, P],
             "nerf_composite_bwd": [P, P, P, I64, I, F, P, P, P, P, P, P],
+            "nerf_image_metrics_tile": [P, P],
+            "nerf_image_metrics_workspace_bytes": [I64, I, I],
+            "nerf_image_metrics": [P, P, P, I64, I, I, I, P, I64, P, P],
             "nerf_grad_sqnorm": [P, I64, P, P],
             "nerf_adam": [P, P, P, P, I64, P, P, I, D, D, F, F, I, P, F, P],
             "nerf_version": [],
@@ -167,6 +170,7 @@ def lib():
         L.nerf_scan_workspace_bytes.restype = c_int64
         L.nerf_occ_threshold_floats.restype = c_int64
         L.nerf_reptile_workspace_bytes.restype = c_int64
+        L.nerf_image_metrics_workspace_bytes.restype = c_int64
         _lib = L
     return _lib
 
@@ -192,7 +196,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_occ_sample_cells", "nerf_moe_route_n", "nerf_ngp_fwd_enc_n", "nerf_ngp_density_enc_rng",
            "nerf_ngp_bwd_hash_n", "nerf_moe_dispatch_n", "nerf_gather_rows_rng", "nerf_moe_blend_rng",
            "nerf_moe_blend_finish_n", "nerf_moe_blend_bwd_rng",
-           "nerf_packed_points_n", "nerf_pick_pixels_dseed", "nerf_adam_dstep", "nerf_occ_march_multi_staged_dseed")
+           "nerf_packed_points_n", "nerf_pick_pixels_dseed", "nerf_adam_dstep", "nerf_occ_march_multi_staged_dseed",
+           "nerf_image_metrics_tile", "nerf_image_metrics_workspace_bytes", "nerf_image_metrics")
 
 
 def check(status: int, what: str) -> None:

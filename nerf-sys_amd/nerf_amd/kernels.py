@@ -268,6 +268,51 @@ def composite_bwd(rgb_sigma, t, bg, g_rgb, g_depth=None, g_acc=None, g_w=None, s
     return out
 
 
+# ------------------------------------------------------------------ image metrics
+
+
+def image_metrics_tile():
+    """(tile_h, tile_w): the SSIM-map pixels one workgroup of nerf_image_metrics covers."""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().nerf_image_metrics_tile(ctypes.byref(th), ctypes.byref(tw)), "nerf_image_metrics_tile")
+    return th.value, tw.value
+
+
+def image_metrics_workspace_bytes(n_img, H, W):
+    return lib().nerf_image_metrics_workspace_bytes(n_img, H, W)
+
+
+def image_metrics(pred, gt, color_space="linear", out=None, ws=None):
+    """nerf_image_metrics: pred (H,W,3) or (N,H,W,3) linear float32 against gt of the same shape, float32 or uint8
+    (8-bit sRGB, v / 255) -> (N,4) float32 = mse, ssim_r, ssim_g, ssim_b in ``color_space``.  ``ws`` is a uint8 device
+    buffer of image_metrics_workspace_bytes(N, H, W) bytes."""
+    need(pred, "pred")
+    need(gt, "gt", torch.uint8 if isinstance(gt, torch.Tensor) and gt.dtype == torch.uint8 else F32)
+    cs = _CS.get(color_space)
+    if cs is None:
+        raise ValueError(f"Invalid color_space={color_space!r}; use 'linear'|'srgb'|'identity'")
+    if pred.dim() not in (3, 4) or pred.shape[-1] != 3:
+        raise ValueError(f"pred must be (H,W,3) or (N,H,W,3), got {tuple(pred.shape)}")
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"gt must have pred's shape {tuple(pred.shape)}, got {tuple(gt.shape)}")
+    n = pred.shape[0] if pred.dim() == 4 else 1
+    H, W = int(pred.shape[-3]), int(pred.shape[-2])
+    if out is None:
+        out = _empty((n, 4), pred)
+    else:
+        need(out, "out")
+        if tuple(out.shape) != (n, 4):
+            raise ValueError(f"out must be ({n},4), got {tuple(out.shape)}")
+    if ws is None:
+        ws = torch.empty(max(int(image_metrics_workspace_bytes(n, H, W)), 0), dtype=torch.uint8, device=pred.device)
+    else:
+        need(ws, "ws", torch.uint8)
+    u8 = gt.dtype == torch.uint8
+    check(lib().nerf_image_metrics(ptr(pred), None if u8 else ptr(gt), ptr(gt) if u8 else None, n, H, W, cs,
+                                   ptr(ws), ws.numel(), ptr(out), stream()), "nerf_image_metrics")
+    return out
+
+
 # ------------------------------------------------------------------ optimiser
 
 

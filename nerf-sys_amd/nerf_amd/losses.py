@@ -85,3 +85,10 @@ def image_psnr(pred_linear, gt_u8_or_srgb, color_space: str = "linear") -> float
     gt = gt_u8_or_srgb.float() / 255.0 if gt_u8_or_srgb.dtype == torch.uint8 else gt_u8_or_srgb.float()
     a, b = color_space_transformer(pred_linear.float(), gt.to(pred_linear.device), color_space)
     return psnr(F.mse_loss(a, b).item())
+
+
+def image_ssim(pred_linear, gt_u8_or_srgb, color_space: str = "linear") -> float:
+    """Full-image SSIM beside image_psnr (runtime_adapt.py:158: pytorch_msssim.ssim, data_range=1, on the same
+    colour-space-transformed pair), mean of the three channels; measured by the HIP kernel behind metrics.image_metrics."""
+    from .metrics import image_metrics
+    return float(image_metrics(pred_linear, gt_u8_or_srgb.to(pred_linear.device), color_space)["ssim"][0])

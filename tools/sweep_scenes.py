@@ -35,16 +35,17 @@ FLOP_PER_RAY = 769327104
 PEAK = {"fp32": 157.3e12, "bf16": 2500e12}
 
 
-def _psnr(coarse, fine, scene, S=64, NI=128):
-    from nerf_amd.losses import image_psnr
+def _psnr_ssim(coarse, fine, scene, S=64, NI=128):
+    from nerf_amd.losses import image_psnr, image_ssim
     from nerf_amd.ray_rendering import render_image
     fx, fy, cx, cy = scene.intrinsics
-    ps = []
+    ps, ss = [], []
     for v in range(scene.test_poses.shape[0]):
         img, _, _ = render_image(coarse, H=scene.H, W=scene.W, fx=fx, fy=fy, cx=cx, cy=cy, c2w=scene.test_poses[v],
                                  near=scene.near, far=scene.far, ray_samples=S, n_importance=NI, fine_model=fine)
         ps.append(image_psnr(img, scene.test_images[v], "linear"))
-    return sum(ps) / len(ps)
+        ss.append(image_ssim(img, scene.test_images[v], "linear"))
+    return sum(ps) / len(ps), sum(ss) / len(ss)
 
 
 def train_scene(sid, *, steps, batch, train_views, test_views, precision, lr, dev, H=800, W=800,
@@ -59,7 +60,7 @@ def train_scene(sid, *, steps, batch, train_views, test_views, precision, lr, de
     coarse, fine = VanillaNeRF().to(dev), VanillaNeRF().to(dev)
     rec = {"scene_seed": sid}
     if initial_psnr:
-        rec["psnr_init"] = round(_psnr(coarse.eval(), fine.eval(), scene), 3)
+        rec["psnr_init"] = round(_psnr_ssim(coarse.eval(), fine.eval(), scene)[0], 3)
     tr = NeRFTrainer(coarse, fine, n_samples=64, n_importance=128, lr_sigma=lr, lr_color=lr, device=dev,
                      precision=precision)
     rb = RayBatcher(scene, dev)
@@ -74,8 +75,9 @@ def train_scene(sid, *, steps, batch, train_views, test_views, precision, lr, de
     tr.sync_to_modules()
     coarse.eval(), fine.eval()
     ls = losses.cpu().tolist()
+    psnr_v, ssim_v = _psnr_ssim(coarse, fine, scene)
     rec.update({"steps": steps, "train_s": round(el, 2), "rays_per_s": round(steps * batch / el, 1),
-                "loss": round(ls[-1], 6), "psnr": round(_psnr(coarse, fine, scene), 3), "losses": ls})
+                "loss": round(ls[-1], 6), "psnr": round(psnr_v, 3), "ssim": round(ssim_v, 4), "losses": ls})
     return rec
 
 

@@ -41,7 +41,7 @@ def main():
     from nerf_amd.trainer import NeRFTrainer, RayBatcher
     from nerf_amd.vanilla import VanillaNeRF
     from nerf_amd.ray_rendering import render_image
-    from nerf_amd.losses import image_psnr
+    from nerf_amd.losses import image_psnr, image_ssim
 
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -61,14 +61,15 @@ def main():
     def evaluate():
         tr.sync_to_modules()
         coarse.eval(), fine.eval()
-        ps = []
+        ps, ss = [], []
         for v in range(scene.test_poses.shape[0]):
             img, _, _ = render_image(coarse, H=scene.H, W=scene.W, fx=fx, fy=fy, cx=cx, cy=cy,
                                      c2w=scene.test_poses[v], near=scene.near, far=scene.far,
                                      ray_samples=a.samples, n_importance=a.importance, fine_model=fine, ndc=ndc)
             ps.append(image_psnr(img, scene.test_images[v], "linear"))
+            ss.append(image_ssim(img, scene.test_images[v], "linear"))
         coarse.train(), fine.train()
-        return sum(ps) / len(ps)
+        return sum(ps) / len(ps), sum(ss) / len(ss)
 
     train_s = 0.0
     step = 0
@@ -82,9 +83,10 @@ def main():
             step += 1
         torch.cuda.synchronize()
         train_s += time.perf_counter() - t0
+        psnr_v, ssim_v = evaluate()
         rec = {"scene": a.scene, "precision": a.precision, "jitter_seed": a.jitter_seed,
                "lib": os.path.basename(os.environ.get("NERF_AMD_LIB", "libnerf_amd.so")), "step": step, "train_s": round(train_s, 2), "loss": round(float(loss.item()), 6),
-               "psnr": round(evaluate(), 3), "rays_per_s": round(step * a.batch / train_s, 1)}
+               "psnr": round(psnr_v, 3), "ssim": round(ssim_v, 4), "rays_per_s": round(step * a.batch / train_s, 1)}
         print(json.dumps(rec), flush=True)
         if outf:
             outf.write(json.dumps(rec) + "\n")
