@@ -298,6 +298,19 @@ int nerf_hash_encode(const NerfHashGrid* grid, const float* table, const float* 
 int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* x, int64_t x_stride, int64_t M, const float* aabb,
                          float enc_eps, const float* d_out, int d_stride, float* d_table, hipStream_t stream);
 
+/* Backward of nerf_hash_encode w.r.t. the POSITION: what autograd gives for HashGridEncoder._torch_forward
+ * (models/encodings.py:313-381) and, with aabb, MetaNGP._world_to_unit (models/inr/meta_ngp.py:166-169).
+ * d_x[m][0..2] = sum over levels (ascending) and features (ascending) of d_out[m][l*F+f] * d enc[l*F+f] / d x; it is
+ * overwritten, columns >= 3 of a wider pitch dx_stride are left untouched.  Cells and weights are the forward's
+ * (same fp32 operations).  Linear (:362-381): resolution times the corner difference along the axis, blended by the
+ * other two axes' weights; Smoothstep (:355-361): that times 6w(1-w) of the raw w on the axis, the other axes with
+ * their smoothed weights; Nearest (:331-353): zeros.  With aabb, component c is divided by the extent where
+ * eps <= (x-min)/extent <= 1-eps (inclusive, torch.clamp's backward) and is exactly 0 elsewhere.  No atomics: equal
+ * inputs give equal bits.  M == 0 is an empty call. */
+int nerf_hash_encode_bwd_x(const NerfHashGrid* grid, const float* table, const float* x, int64_t x_stride, int64_t M,
+                           const float* aabb, float enc_eps, const float* d_out, int d_stride, float* d_x,
+                           int64_t dx_stride, hipStream_t stream);
+
 /* SHEncoder.forward (models/encodings.py:133-151, components :27-81): normalise (clamp 1e-9), real SH of
  * degree levels-1 (levels 1..5) -> out (M rows, pitch out_stride >= levels^2). */
 int nerf_sh_encode(const float* d, int64_t d_stride, int64_t M, int levels, float* out, int out_stride,
@@ -352,6 +365,19 @@ int nerf_ngp_fwd_enc(const NerfNgpNet* net, const NerfHashGrid* grid, const floa
 int nerf_ngp_density_enc(const NerfNgpNet* net, const NerfHashGrid* grid, const float* table, const float* w,
                          const float* x, int64_t x_stride, int64_t M, const float* aabb, float enc_eps, float* sigma,
                          hipStream_t stream);
+
+/* sigma AND its spatial gradient at world points in ONE launch for the shapes nerf_ngp_density_enc supports
+ * (NERF_E_UNSUPPORTED otherwise, answered before any buffer is looked at): autograd of MetaNGP.density
+ * (models/inr/meta_ngp.py:203-239) w.r.t. x, through trunc_exp's backward exp(clamp(raw)) (models/trunc_exp.py:54-57),
+ * the sigma head and trunk (ReLU masks of the forward) and the encoding's Jacobian (nerf_hash_encode_bwd_x).
+ * sigma (M) is bitwise nerf_ngp_density_enc's; grad (M rows, pitch grad_stride >= 3): columns 0..2 = d sigma / d x,
+ * further columns untouched.  ws (16-byte aligned, nerf_ngp_density_grad_workspace_bytes(net) bytes) receives the
+ * transposed trunk weights in a small launch of its own ahead of the kernel. */
+int64_t nerf_ngp_density_grad_workspace_bytes(const NerfNgpNet* net);
+int nerf_ngp_density_grad_enc(const NerfNgpNet* net, const NerfHashGrid* grid, const float* table, const float* w,
+                              const float* x, int64_t x_stride, int64_t M, const float* aabb, float enc_eps,
+                              float* sigma, float* grad, int64_t grad_stride, void* ws, int64_t ws_bytes,
+                              hipStream_t stream);
 
 /* Backward of nerf_ngp_fwd (recomputes the forward on chip): d_enc (M rows, pitch enc_stride; cols
  * >= in_dim untouched) and d_w (packed layout; overwritten, or accumulated into if accumulate != 0). */

@@ -215,10 +215,13 @@ __device__ __forceinline__ void load_x01(const HashArgs& a, const float* __restr
 
 // corner weights in the reference's autograd product order: ((g*(1-wz))*(1-wy))*(1-wx) etc.  For the
 // forward the blend is c00 = f000*(1-wx) + f100*wx, ... (no fma contraction: bit-exact with torch).
-// the F features of one level at unit-cube point p (shared by hash_fwd_kernel and the fused density kernel)
-template <int F>
-__device__ __forceinline__ void hash_level(const HashArgs& a, const float* __restrict__ table, const float p[3], int l,
-                                           float acc[F]) {
+// the F features of one level at unit-cube point p (shared by hash_fwd_kernel and the fused density kernel).
+// JAC: also their spatial Jacobian J[f][c] = d acc[f] / d p[c], from the same cell and the same weights: the corner
+// difference along axis c blended by the other two axes' weights, times d w_c / d p_c = r (Linear) or
+// r * 6 w (1 - w) of the raw w (Smoothstep: the derivative of w w (3 - 2 w)); Nearest is piecewise constant, J = 0.
+template <int F, bool JAC>
+__device__ __forceinline__ void hash_level_core(const HashArgs& a, const float* __restrict__ table, const float p[3],
+                                                int l, float acc[F], float (*J)[3]) {
   const float r = (float)a.res[l];
   const uint32_t mask = (1u << a.log2T) - 1u;
   const float* tb = table + ((int64_t)l << a.log2T) * F;
@@ -227,8 +230,12 @@ __device__ __forceinline__ void hash_level(const HashArgs& a, const float* __res
     const float* e = tb + (int64_t)ngp_hash(ix, iy, iz, mask) * F;
 #pragma unroll
     for (int f = 0; f < F; ++f) acc[f] = e[f];
+    if constexpr (JAC) {
+#pragma unroll
+      for (int f = 0; f < F; ++f) J[f][0] = J[f][1] = J[f][2] = 0.f;
+    }
   } else {
-    float s[3], w[3];
+    float s[3], w[3], dw[3];
     int i0[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -236,6 +243,7 @@ __device__ __forceinline__ void hash_level(const HashArgs& a, const float* __res
       const float fl = floorf(s[c]);
       w[c] = __fsub_rn(s[c], fl);
       i0[c] = (int)fl;
+      if constexpr (JAC) dw[c] = a.interp == 2 ? r * (6.0f * w[c] * (1.0f - w[c])) : r;
       if (a.interp == 2) w[c] = __fmul_rn(__fmul_rn(w[c], w[c]), __fsub_rn(3.0f, __fmul_rn(2.0f, w[c])));
     }
     float f[8][F];
@@ -265,8 +273,42 @@ __device__ __forceinline__ void hash_level(const HashArgs& a, const float* __res
       const float c0 = __fadd_rn(__fmul_rn(c00, uy), __fmul_rn(c10, w[1]));
       const float c1 = __fadd_rn(__fmul_rn(c01, uy), __fmul_rn(c11, w[1]));
       acc[q] = __fadd_rn(__fmul_rn(c0, uz), __fmul_rn(c1, w[2]));
+      if constexpr (JAC) {
+        const float e0 = (f[4][q] - f[0][q]) * uy + (f[6][q] - f[2][q]) * w[1];
+        const float e1 = (f[5][q] - f[1][q]) * uy + (f[7][q] - f[3][q]) * w[1];
+        J[q][0] = (e0 * uz + e1 * w[2]) * dw[0];
+        J[q][1] = ((c10 - c00) * uz + (c11 - c01) * w[2]) * dw[1];
+        J[q][2] = (c1 - c0) * dw[2];
+      }
     }
   }
+}
+
+template <int F>
+__device__ __forceinline__ void hash_level(const HashArgs& a, const float* __restrict__ table, const float p[3], int l,
+                                           float acc[F]) {
+  hash_level_core<F, false>(a, table, p, l, acc, nullptr);
+}
+
+// One level's share of d_x (unit-cube coordinates): t[c] = sum over the features, ascending, of g[f] J[f][c]
+template <int F>
+__device__ __forceinline__ void hash_dx_level(const float (*J)[3], const float g[F], float t[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float s = g[0] * J[0][c];
+#pragma unroll
+    for (int f = 1; f < F; ++f) s += g[f] * J[f][c];
+    t[c] = s;
+  }
+}
+
+// d (unit-cube coordinate c) -> d (world coordinate c) of row m: the backward of load_x01.  torch.clamp passes the
+// gradient where eps <= v <= 1 - eps (bounds inclusive) and gives exactly 0 outside; then the division by the extent.
+__device__ __forceinline__ float x01_grad(const HashArgs& a, const float* __restrict__ x, int64_t xs, int64_t m, int c,
+                                          float d) {
+  if (!a.has_aabb) return d;
+  const float v = __fdiv_rn(__fsub_rn(x[m * xs + c], a.mn[c]), a.ext[c]);
+  return (v >= a.eps && v <= 1.0f - a.eps) ? __fdiv_rn(d, a.ext[c]) : 0.f;
 }
 
 template <int F>
@@ -289,6 +331,31 @@ __global__ void hash_fwd_kernel(HashArgs a, const float* __restrict__ table, con
   }
   // zero the row's pad columns [L*F, os): spread over the row's L threads
   for (int c = a.L * F + l; c < os; c += a.L) out[m * os + c] = 0.f;
+}
+
+// Backward of the encoding w.r.t. the position: one thread per sample walks the levels in ascending order and adds
+// each level's share (hash_dx_level: features ascending), so the sum has one fixed order and no atomics.
+template <int F>
+__global__ __launch_bounds__(256) void hash_bwd_x_kernel(HashArgs a, const float* __restrict__ table,
+                                                         const float* __restrict__ x, int64_t xs, int64_t M,
+                                                         const float* __restrict__ g, int gs, float* __restrict__ dx,
+                                                         int64_t dxs) {
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  float p[3];
+  load_x01(a, x, xs, m, p);
+  float d[3] = {0.f, 0.f, 0.f};
+  for (int l = 0; l < a.L; ++l) {
+    float acc[F], J[F][3], gg[F], t[3];
+    hash_level_core<F, true>(a, table, p, l, acc, J);
+#pragma unroll
+    for (int q = 0; q < F; ++q) gg[q] = g[m * gs + l * F + q];
+    hash_dx_level<F>(J, gg, t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] += t[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dx[m * dxs + c] = x01_grad(a, x, xs, m, c, d[c]);
 }
 
 template <int F>
@@ -1108,21 +1175,24 @@ __device__ __forceinline__ void fwd(float* smem, const NgpFrag& f, int wave, int
   }
 }
 
-template <int l, bool ENC_TO_LDS = false>
+// G / GN / XIN / ENCT: the gradient tile read, the one written, the layer-input tile of the ReLU mask and the d_enc
+// tile (the backward plan's by default; the density-gradient kernel has a plan of its own).  GN == XIN is allowed:
+// each lane masks and overwrites its own four elements.
+template <int l, bool ENC_TO_LDS = false, int G = GB[l], int GN = GNB[l], int XIN = INB[l], int ENCT = G1>
 __device__ __forceinline__ void dgrad(float* smem, const NgpFrag& f, int wave, int lane, float* __restrict__ d_enc,
                                       int es, int in_dim, int64_t m0, int64_t M) {
   constexpr int NRB = KP[l] == 64 ? 2 : 1;
   const int g = lane >> 4, c16 = lane & 15;
   const int kb = KP[l] == 64 ? wave : (wave & 1), rb0 = KP[l] == 64 ? 0 : (wave >> 1);
   float4 acc[2];
-  mfma16_tile<NE[l] / 16, NRB>(acc, f, smem + GB[l] + (16 * rb0 + c16) * 68 + 4 * g, 68);
+  mfma16_tile<NE[l] / 16, NRB>(acc, f, smem + G + (16 * rb0 + c16) * 68 + 4 * g, 68);
   const int k0 = kb * 16 + 4 * g;
 #pragma unroll
   for (int b = 0; b < NRB; ++b) {
     const int r = 16 * (rb0 + b) + c16;
     float v0 = acc[b].x, v1 = acc[b].y, v2 = acc[b].z, v3 = acc[b].w;
     if constexpr (l == 0 && ENC_TO_LDS) {  // d_enc tile -> the free gradient tile (G1) for the fused table scatter
-      *reinterpret_cast<float4*>(smem + G1 + r * 68 + k0) = make_float4(v0, v1, v2, v3);
+      *reinterpret_cast<float4*>(smem + ENCT + r * 68 + k0) = make_float4(v0, v1, v2, v3);
     } else if constexpr (l == 0) {
       const int64_t m = m0 + r;
       if (m < M) {
@@ -1134,10 +1204,10 @@ __device__ __forceinline__ void dgrad(float* smem, const NgpFrag& f, int wave, i
       }
     } else {
       if (INRELU[l]) {
-        const float4 x = *reinterpret_cast<const float4*>(smem + INB[l] + r * INLD[l] + k0);
+        const float4 x = *reinterpret_cast<const float4*>(smem + XIN + r * INLD[l] + k0);
         v0 = x.x > 0.f ? v0 : 0.f; v1 = x.y > 0.f ? v1 : 0.f; v2 = x.z > 0.f ? v2 : 0.f; v3 = x.w > 0.f ? v3 : 0.f;
       }
-      *reinterpret_cast<float4*>(smem + GNB[l] + r * 68 + k0) = make_float4(v0, v1, v2, v3);
+      *reinterpret_cast<float4*>(smem + GN + r * 68 + k0) = make_float4(v0, v1, v2, v3);
     }
   }
 }
@@ -1567,6 +1637,106 @@ __global__ __launch_bounds__(256) void ngp_density_enc_prod_kernel(HashArgs a, c
   }
 }
 
+// sigma and d sigma / d x at world points for the production expert, one launch: ngp_density_enc_prod_kernel's
+// prologue and forward (the same code, so sigma has the same bits), then the sigma branch's input-gradient chain
+// back to the encoding, contracted with the encoding's spatial Jacobian.
+//   LDS plan (floats): enc [32][36] | h0 [32][68] | h1 [32][68] | head out [32][68] | 30.8 KB per workgroup.  The
+//   gradients reuse the activation tiles: d h1 = d sigma_raw W_head[0, :] masked by h1 > 0 overwrites h1 in place
+//   (elementwise), dgrad<1> reads it and overwrites h0 with d h0 in place (each lane masks and writes its own four
+//   elements), dgrad<0> writes d enc over d h1, and the head tile then takes the per-level shares of d x.
+//   The Jacobian stays in REGISTERS: the thread that encodes (row, level) pairs t and t + 256 in the prologue
+//   contracts the same pairs at the end (2 x 2 features x 3 axes = 12 VGPRs across the MLP) — no Jacobian tile in
+//   LDS (it would be [32][32][3] = 12 KB) and no second gather of the table.
+// Rows past M read row M - 1 and are never stored.
+namespace ngp_prod {
+constexpr int D_ENC = 0, D_H0 = 1152, D_H1 = 3328, D_HD = 5504, D_SMEM = 7680;
+// pitch of the d x shares [32][16 levels x 3 + 1]: odd, so the 96 summing threads spread over the banks
+constexpr int D_PLD = 49;
+}
+
+__global__ __launch_bounds__(256) void ngp_density_grad_prod_kernel(HashArgs a, const float* __restrict__ table,
+                                                                    const float* __restrict__ w,
+                                                                    const float* __restrict__ wt,
+                                                                    const float* __restrict__ x, int64_t xs,
+                                                                    int64_t M, float* __restrict__ sigma,
+                                                                    float* __restrict__ grad, int64_t gs) {
+  using namespace ngp_prod;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  if ((int64_t)blockIdx.x * NGP_BROWS >= M) return;  // whole workgroup: no barrier is left waiting
+  const int64_t m0 = (int64_t)blockIdx.x * NGP_BROWS;
+  NgpFrag fa, fb;
+  load_frag<0>(w, wt, wave, lane, fa);
+  load_frag<1>(w, wt, wave, lane, fb);
+  float J[2][2][3];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int pair = tid + 256 * u, r = pair >> 4, l = pair & 15;
+    const int64_t m = m0 + r < M ? m0 + r : M - 1;
+    float2 v = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int f = 0; f < 2; ++f) J[u][f][0] = J[u][f][1] = J[u][f][2] = 0.f;
+    if (l < a.L) {
+      float p[3], acc[2];
+      load_x01(a, x, xs, m, p);
+      hash_level_core<2, true>(a, table, p, l, acc, J[u]);
+      v = make_float2(acc[0], acc[1]);
+    }
+    *reinterpret_cast<float2*>(smem + D_ENC + r * 36 + 2 * l) = v;
+  }
+  lds_barrier();
+  fwd<0, D_ENC, 36, D_H0>(smem, fa, wave, lane);
+  lds_barrier();
+  load_frag<2>(w, wt, wave, lane, fa);
+  fwd<1, D_H0, 68, D_H1>(smem, fb, wave, lane);
+  lds_barrier();
+  load_frag<2 * NL - 2>(w, wt, wave, lane, fb);  // the input-gradient step of layer 1
+  fwd<2, D_H1, 68, D_HD>(smem, fa, wave, lane);
+  lds_barrier();
+  load_frag<2 * NL - 1>(w, wt, wave, lane, fa);  // ... of layer 0
+  {
+    // sigma = trunc_exp(raw), d sigma / d raw = exp(clamp(raw)) (trunc_exp.py:54-57; ngp_bwd_prod_kernel's expression
+    // with an output gradient of 1), and the head's rank-1 input gradient: thread (pr, pp) owns row pr's columns
+    // 8 pp .. 8 pp + 7 of h1
+    const int pr = tid >> 3, pp = tid & 7;
+    const float sr = smem[D_HD + pr * 68];
+    const float ds = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+    if (pp == 0 && m0 + pr < M) sigma[m0 + pr] = ds;
+    const float4 w0 = *reinterpret_cast<const float4*>(w + WOFF[HEAD] + 8 * pp);
+    const float4 w1 = *reinterpret_cast<const float4*>(w + WOFF[HEAD] + 8 * pp + 4);
+    float4* h = reinterpret_cast<float4*>(smem + D_H1 + pr * 68 + 8 * pp);
+    const float4 h0 = h[0], h1 = h[1];
+    h[0] = make_float4(h0.x > 0.f ? ds * w0.x : 0.f, h0.y > 0.f ? ds * w0.y : 0.f, h0.z > 0.f ? ds * w0.z : 0.f,
+                       h0.w > 0.f ? ds * w0.w : 0.f);
+    h[1] = make_float4(h1.x > 0.f ? ds * w1.x : 0.f, h1.y > 0.f ? ds * w1.y : 0.f, h1.z > 0.f ? ds * w1.z : 0.f,
+                       h1.w > 0.f ? ds * w1.w : 0.f);
+  }
+  lds_barrier();
+  dgrad<1, false, D_H1, D_H0, D_H0>(smem, fb, wave, lane, nullptr, 0, 0, m0, M);
+  lds_barrier();
+  dgrad<0, true, D_H0, -1, D_ENC, D_H1>(smem, fa, wave, lane, nullptr, 0, 0, m0, M);
+  lds_barrier();
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int pair = tid + 256 * u, r = pair >> 4, l = pair & 15;
+    const float2 g = *reinterpret_cast<const float2*>(smem + D_H1 + r * 68 + 2 * l);
+    const float gg[2] = {g.x, g.y};
+    float t[3];
+    hash_dx_level<2>(J[u], gg, t);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) smem[D_HD + r * D_PLD + 3 * l + c] = t[c];
+  }
+  lds_barrier();
+  if (tid < 3 * NGP_BROWS) {  // thread (row, axis): the levels in ascending order, as hash_bwd_x_kernel
+    const int r = tid / 3, c = tid - 3 * r;
+    if (m0 + r < M) {
+      float d = 0.f;
+      for (int l = 0; l < a.L; ++l) d += smem[D_HD + r * D_PLD + 3 * l + c];
+      grad[(m0 + r) * gs + c] = x01_grad(a, x, xs, m0 + r, c, d);
+    }
+  }
+}
+
 // dw = sum over the workgroup slabs.  A block owns 64 consecutive columns (16 float4) and 16 slab groups: thread
 // (g, c) sums slabs g, g+16, ... of its column in order, then column c's 16 group sums are added in order g = 0..15
 // (deterministic).  One thread per column over all slabs ran at 0.3 TB/s (256 dependent adds per thread).
@@ -1728,6 +1898,38 @@ extern "C" int nerf_hash_encode_bwd(const NerfHashGrid* grid, const float* x, in
   return nerf_launch_status();
 }
 
+extern "C" int nerf_hash_encode_bwd_x(const NerfHashGrid* grid, const float* table, const float* x, int64_t x_stride,
+                                      int64_t M, const float* aabb, float enc_eps, const float* d_out, int d_stride,
+                                      float* d_x, int64_t dx_stride, hipStream_t st) {
+  HashArgs a;
+  if (!hash_args(grid, nullptr, a) || M < 0 || x_stride < 3 || d_stride < a.L * a.F || dx_stride < 3)
+    return NERF_E_ARG;
+  if (M == 0) return NERF_OK;
+  if (!table || !x || !d_out || !d_x) return NERF_E_ARG;
+  if (aabb) {
+    a.has_aabb = 1;
+    for (int c = 0; c < 3; ++c) { a.mn[c] = aabb[c]; a.ext[c] = aabb[3 + c] - aabb[c]; }
+    a.eps = enc_eps;
+  }
+  if ((a.F == 2 || a.F == 4) && !nerf_aligned16(table)) return NERF_E_ALIGN;
+  const unsigned blocks = (unsigned)nerf_cdiv(M, 256);
+  switch (a.F) {
+    case 1:
+      hash_bwd_x_kernel<1><<<blocks, 256, 0, st>>>(a, table, x, x_stride, M, d_out, d_stride, d_x, dx_stride);
+      break;
+    case 2:
+      hash_bwd_x_kernel<2><<<blocks, 256, 0, st>>>(a, table, x, x_stride, M, d_out, d_stride, d_x, dx_stride);
+      break;
+    case 4:
+      hash_bwd_x_kernel<4><<<blocks, 256, 0, st>>>(a, table, x, x_stride, M, d_out, d_stride, d_x, dx_stride);
+      break;
+    default:
+      hash_bwd_x_kernel<8><<<blocks, 256, 0, st>>>(a, table, x, x_stride, M, d_out, d_stride, d_x, dx_stride);
+      break;
+  }
+  return nerf_launch_status();
+}
+
 extern "C" int nerf_sh_encode(const float* d, int64_t d_stride, int64_t M, int levels, float* out, int out_stride,
                               hipStream_t st) {
   if (M < 0 || d_stride < 3 || levels < 1 || levels > 5 || out_stride < levels * levels) return NERF_E_ARG;
@@ -1839,6 +2041,38 @@ extern "C" int nerf_ngp_density_enc_rng(const NerfNgpNet* net, const NerfHashGri
                                         hipStream_t st) {
   if (!rng) return NERF_E_ARG;
   return ngp_density_enc_impl(net, grid, table, w, x, x_stride, cap, rng, aabb, enc_eps, sigma, st);
+}
+
+extern "C" int64_t nerf_ngp_density_grad_workspace_bytes(const NerfNgpNet* net) {
+  NgpPlan P;
+  if (!net || !make_plan(*net, true, P)) return NERF_E_ARG;
+  return P.total * 4;  // the W^T image
+}
+
+extern "C" int nerf_ngp_density_grad_enc(const NerfNgpNet* net, const NerfHashGrid* grid, const float* table,
+                                         const float* w, const float* x, int64_t x_stride, int64_t M,
+                                         const float* aabb, float enc_eps, float* sigma, float* grad,
+                                         int64_t grad_stride, void* ws, int64_t ws_bytes, hipStream_t st) {
+  NgpPlan Pb;
+  HashArgs a;
+  if (!net || !grid || M < 0 || x_stride < 3 || grad_stride < 3 || !make_plan(*net, true, Pb) ||
+      !hash_args(grid, nullptr, a))
+    return NERF_E_ARG;
+  if (a.F != 2 || a.L > 16 || a.L * a.F != net->in_dim || !is_prod_plan(*net, Pb)) return NERF_E_UNSUPPORTED;
+  if (M == 0) return NERF_OK;
+  if (!table || !w || !x || !sigma || !grad || !ws) return NERF_E_ARG;
+  if (!nerf_aligned16(w) || !nerf_aligned16(table) || !nerf_aligned16(ws)) return NERF_E_ALIGN;
+  if (ws_bytes < Pb.total * 4) return NERF_E_WORKSPACE;
+  if (aabb) {
+    a.has_aabb = 1;
+    for (int c = 0; c < 3; ++c) { a.mn[c] = aabb[c]; a.ext[c] = aabb[3 + c] - aabb[c]; }
+    a.eps = enc_eps;
+  }
+  float* wt = reinterpret_cast<float*>(ws);
+  ngp_wt_kernel<<<ngp_prod::HEAD, 256, 0, st>>>(Pb, w, wt);  // W^T of the two trunk layers (the head is rank 1)
+  ngp_density_grad_prod_kernel<<<(unsigned)nerf_cdiv(M, NGP_BROWS), 256, (size_t)ngp_prod::D_SMEM * 4, st>>>(
+      a, table, w, wt, x, x_stride, M, sigma, grad, grad_stride);
+  return nerf_launch_status();
 }
 
 static int ngp_fwd_enc_impl(const NerfNgpNet* net, const NerfHashGrid* grid, const float* table, const float* w,

@@ -88,12 +88,15 @@ def lib():
             "nerf_version": [],
             "nerf_hash_encode": [P, P, P, I64, I64, P, F, P, I, P],
             "nerf_hash_encode_bwd": [P, P, I64, I64, P, F, P, I, P, P],
+            "nerf_hash_encode_bwd_x": [P, P, P, I64, I64, P, F, P, I, P, I64, P],
             "nerf_sh_encode": [P, I64, I64, I, P, I, P],
             "nerf_ngp_layout": [P, P, P],
             "nerf_ngp_workspace_bytes": [P, I64],
             "nerf_ngp_fwd": [P, P, P, I, P, I64, P, P],
             "nerf_ngp_density": [P, P, P, I, I64, P, P],
             "nerf_ngp_density_enc": [P, P, P, P, P, I64, I64, P, F, P, P],
+            "nerf_ngp_density_grad_workspace_bytes": [P],
+            "nerf_ngp_density_grad_enc": [P, P, P, P, P, I64, I64, P, F, P, P, I64, P, I64, P],
             "nerf_ngp_fwd_enc": [P, P, P, P, P, I64, P, F, P, I, P, P],
             "nerf_ngp_bwd_hash": [P, P, P, P, I, P, I64, P, P, F, P, P, I, P, I64, P],
             "nerf_ngp_fwd_enc_n": [P, P, P, P, P, I64, P, P, F, P, I, P, P],
@@ -165,6 +168,7 @@ def lib():
         L.nerf_version.restype = ctypes.c_char_p
         L.nerf_ngp_layout.restype = c_int64
         L.nerf_ngp_workspace_bytes.restype = c_int64
+        L.nerf_ngp_density_grad_workspace_bytes.restype = c_int64
         L.nerf_moe_dispatch_workspace_bytes.restype = c_int64
         L.nerf_bg_mlp_workspace_bytes.restype = c_int64
         L.nerf_scan_workspace_bytes.restype = c_int64
@@ -197,7 +201,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_ngp_bwd_hash_n", "nerf_moe_dispatch_n", "nerf_gather_rows_rng", "nerf_moe_blend_rng",
            "nerf_moe_blend_finish_n", "nerf_moe_blend_bwd_rng",
            "nerf_packed_points_n", "nerf_pick_pixels_dseed", "nerf_adam_dstep", "nerf_occ_march_multi_staged_dseed",
-           "nerf_image_metrics_tile", "nerf_image_metrics_workspace_bytes", "nerf_image_metrics")
+           "nerf_image_metrics_tile", "nerf_image_metrics_workspace_bytes", "nerf_image_metrics",
+           "nerf_hash_encode_bwd_x", "nerf_ngp_density_grad_workspace_bytes", "nerf_ngp_density_grad_enc")
 
 
 def check(status: int, what: str) -> None:

@@ -27,6 +27,7 @@ class FrequencyEncoder(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         assert x.shape[-1] == self.in_dim, f"Expected (...,{self.in_dim}), got {tuple(x.shape)}"
         if x.requires_grad and torch.is_grad_enabled():
+            # still out of scope: only the hash-grid encoding has a position gradient (ngp.hash_encode_bwd_x)
             raise NotImplementedError("FrequencyEncoder (HIP) has no input gradient")
         xin = x.float().contiguous()
         if self.use_pi:

@@ -118,6 +118,24 @@ def hash_encode_bwd(grid: NerfHashGrid, x, d_out, n_table_rows, aabb=None, enc_e
     return d_table
 
 
+def hash_encode_bwd_x(grid: NerfHashGrid, table, x, d_out, aabb=None, enc_eps=1e-6, d_x=None):
+    """nerf_hash_encode_bwd_x: the encoding's gradient w.r.t. the positions, d_x[:, :3] (M, >=3; columns >= 3 of a
+    given d_x are left as they are).  d_out (M, >= L*F) rows of pitch d_out.stride(0)."""
+    need(table, "hash_table")
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    if d_out.stride(-1) != 1:
+        d_out = d_out.contiguous()
+    M = x.shape[0]
+    if d_x is None:
+        d_x = torch.empty((M, 3), dtype=torch.float32, device=x.device)
+    ab = (ctypes.c_float * 6)(*[float(v) for v in aabb]) if aabb is not None else None
+    check(lib().nerf_hash_encode_bwd_x(_addr(grid), ptr(table), ptr(x), x.stride(0), M, ab, float(enc_eps),
+                                       ptr(d_out), d_out.stride(0), ptr(d_x), d_x.stride(0), stream()),
+          "nerf_hash_encode_bwd_x")
+    return d_x
+
+
 def sh_encode(d, levels=4):
     if d.stride(-1) != 1:
         d = d.contiguous()
@@ -172,6 +190,31 @@ def ngp_density_enc(net: NerfNgpNet, grid: NerfHashGrid, table, w_packed, x, aab
         return None
     check(rc, "nerf_ngp_density_enc")
     return out
+
+
+def ngp_density_grad_enc(net: NerfNgpNet, grid: NerfHashGrid, table, w_packed, x, aabb=None, enc_eps=1e-6, grad=None):
+    """nerf_ngp_density_grad_enc: world points (M, >=3) -> (sigma (M,), grad (M, >=3) with d sigma / d x in columns
+    0..2) in one launch, or None when the expert's shape has no fused kernel (the caller then composes hash_encode,
+    ngp_bwd and hash_encode_bwd_x)."""
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    M = x.shape[0]
+    sig = torch.empty(M, dtype=torch.float32, device=x.device)
+    if grad is None:
+        grad = torch.empty((M, 3), dtype=torch.float32, device=x.device)
+    need_b = max(int(lib().nerf_ngp_density_grad_workspace_bytes(_addr(net))), 16)
+    key = ("density_grad", str(x.device), torch.cuda.current_stream(x.device).cuda_stream)
+    ws = _WS.get(key)
+    if ws is None or ws.numel() < need_b:
+        ws = _WS[key] = torch.empty(need_b, dtype=torch.uint8, device=x.device)
+    ab = (ctypes.c_float * 6)(*[float(v) for v in aabb]) if aabb is not None else None
+    rc = lib().nerf_ngp_density_grad_enc(_addr(net), _addr(grid), ptr(table), ptr(w_packed), ptr(x), x.stride(0), M,
+                                         ab, float(enc_eps), ptr(sig), ptr(grad), grad.stride(0), ptr(ws), ws.numel(),
+                                         stream())
+    if rc == E_UNSUPPORTED:
+        return None
+    check(rc, "nerf_ngp_density_grad_enc")
+    return sig, grad
 
 
 def ngp_density(net: NerfNgpNet, w_packed, enc):
@@ -242,18 +285,25 @@ class _HashEncodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, table, grid, aabb, eps):
         ctx.grid, ctx.aabb, ctx.eps = grid, aabb, eps
-        ctx.save_for_backward(x)
+        if ctx.needs_input_grad[0]:  # d_x gathers the table again
+            ctx.save_for_backward(x, table)
+        else:
+            ctx.save_for_backward(x)
         ctx.rows = table.shape[0]
         return hash_encode(grid, table.detach(), x, aabb, eps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        (x,) = ctx.saved_tensors
+        """First order only (once_differentiable): the position gradient is itself not differentiable here."""
+        x = ctx.saved_tensors[0]
+        g = g.contiguous()
+        d_x = d_table = None
         if ctx.needs_input_grad[0]:
-            raise NotImplementedError("HashGridEncoder (HIP): no gradient w.r.t. positions")
-        d_table = hash_encode_bwd(ctx.grid, x, g.contiguous(), ctx.rows, ctx.aabb, ctx.eps)
-        return None, d_table, None, None, None
+            d_x = hash_encode_bwd_x(ctx.grid, ctx.saved_tensors[1].detach(), x, g, ctx.aabb, ctx.eps)
+        if ctx.needs_input_grad[1]:
+            d_table = hash_encode_bwd(ctx.grid, x, g, ctx.rows, ctx.aabb, ctx.eps)
+        return d_x, d_table, None, None, None
 
 
 class HashGridEncoder(nn.Module):
@@ -488,6 +538,8 @@ class _NgpFn(torch.autograd.Function):
         x_d, enc, w_packed = ctx.saved_tensors
         model = ctx.model
         if ctx.needs_input_grad[0]:
+            # the gradient of sigma w.r.t. the positions exists for frozen parameters (InstantNGP.density /
+            # density_grad); gradients of rgb w.r.t. x_d, w.r.t. the directions and second order do not
             raise NotImplementedError("InstantNGP (HIP): no gradient w.r.t. sample positions x_d")
         g = g.contiguous().float()
         if x_d.shape[0] == 0:
@@ -533,6 +585,24 @@ def _table_grad_ready(t):
     cb = getattr(t, "_nerf_grad_ready", None)
     if cb is not None:
         cb(t)
+
+
+class _DensityXFn(torch.autograd.Function):
+    """sigma(x) with frozen parameters, differentiable once w.r.t. x: the forward keeps d sigma / d x
+    (InstantNGP.density_grad), the backward scales it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, model, params):
+        sig, grad = model.density_grad(x, params)
+        ctx.save_for_backward(grad)
+        ctx.x_dtype = x.dtype
+        return sig
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (g * grad).to(ctx.x_dtype), None, None
 
 
 class _Block(nn.Module):
@@ -642,6 +712,10 @@ class InstantNGP(nn.Module):
         xf = x.reshape(-1, 3).float()
         w = self.packed(params)
         if not (torch.is_grad_enabled() and (w.requires_grad or self.xyz_encoder.hash_table.requires_grad)):
+            if torch.is_grad_enabled() and x.requires_grad:
+                # frozen parameters, differentiable positions: x.grad = g * d sigma / d x (first order).  When a
+                # parameter needs a gradient too, the full forward below still raises for x.
+                return _DensityXFn.apply(x, self, params)
             # no graph needed (visibility filter, occupancy update): sigma branch only
             with torch.no_grad():
                 h = TIMING.start("density_enc", xf.shape[0])
@@ -661,6 +735,44 @@ class InstantNGP(nn.Module):
         xd = torch.cat([xf, torch.zeros_like(xf)], -1)
         xd[:, 5] = 1.0
         return self.forward(xd, params=params)[:, 3:4].view(*shp, 1)
+
+    def _density_grad_composed(self, xf, w, table):
+        """density_grad from the general kernels, for shapes without the fused launch (and its reference in the
+        tests): hash_encode -> ngp_density (sigma) and ngp_bwd with an output gradient of [0, 0, 0, 1] (d_enc; the
+        colour branch contributes exact zeros, the direction is any unit vector) -> hash_encode_bwd_x."""
+        g, net = self.xyz_encoder.grid, self.net_struct
+        M = xf.shape[0]
+        enc = hash_encode(g, table, xf, self._aabb_host, self._eps)
+        xd = torch.zeros((M, 6), dtype=torch.float32, device=xf.device)
+        xd[:, :3] = xf
+        xd[:, 5] = 1.0
+        d_out = torch.zeros((M, 4), dtype=torch.float32, device=xf.device)
+        d_out[:, 3] = 1.0
+        sig = ngp_density(net, w, enc)
+        d_enc, _ = ngp_bwd(net, w, enc, xd, d_out)
+        return sig, hash_encode_bwd_x(g, table, xf, d_enc, self._aabb_host, self._eps)
+
+    def density_grad(self, x: torch.Tensor, params=None):
+        """(sigma (...,1), d sigma / d x (...,3)) at world points: values only (no graph), first order.  One fused
+        launch for the production shape, else the composed general kernels.  Out of scope here: gradients of rgb
+        w.r.t. the positions, gradients w.r.t. the directions, second order."""
+        shp = x.shape[:-1]
+        with torch.no_grad():
+            xf = x.detach().reshape(-1, 3).float()
+            w = self.packed(params).detach()
+            table = self.xyz_encoder.hash_table.detach()
+            h = TIMING.start("density_grad_enc", xf.shape[0])
+            out = ngp_density_grad_enc(self.net_struct, self.xyz_encoder.grid, table, w, xf, self._aabb_host,
+                                       self._eps)
+            TIMING.stop(h)
+            if out is None:
+                out = self._density_grad_composed(xf, w, table)
+        return out[0].view(*shp, 1), out[1].view(*shp, 3)
+
+    def normals(self, x: torch.Tensor, params=None) -> torch.Tensor:
+        """Unit surface normals -grad / max(|grad|, 1e-12) of the density field (zero where the gradient is zero)."""
+        g = self.density_grad(x, params)[1]
+        return -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
 
     def _anneal_alpha_thre(self, step: int) -> None:
         if step < self.occ_warmup_steps:

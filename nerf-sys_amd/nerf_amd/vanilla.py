@@ -142,6 +142,7 @@ class VanillaMLPFn(torch.autograd.Function):
         d_w = K.mlp_bwd(w_packed, ctx.M, g, ctx.ws, precision=ctx.precision)
         ctx.ws = None
         if ctx.needs_input_grad[0]:
+            # still out of scope: only the Instant-NGP expert has a position gradient (InstantNGP.density_grad)
             raise NotImplementedError("gradient w.r.t. sample positions x_d is not supported by the HIP MLP")
         return None, d_w, None
 
