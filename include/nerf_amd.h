@@ -634,6 +634,26 @@ int nerf_dataset_rays(const float* c2w, const float* intrinsics, const int32_t* 
                       float far_v, const uint8_t* images, const uint8_t* masks, int32_t* flags, const int32_t* pos,
                       float* out_rays, float* out_rgb, int32_t* out_idx, hipStream_t stream);
 
+/* ------------------------------------------------------------------ mesh extraction */
+
+/* Marching tetrahedra over the Kuhn split of a lattice of densities: field (nx,ny,nz) contiguous fp32, linear index
+ * p = (ix ny + iy) nz + iz, every dimension >= 2 and 12 nx ny nz < 2^31 (else NERF_E_ARG); a point is inside iff
+ * field > iso (the field must be finite; the kernels do not check).  Point p owns the edges to p + d, d = 1..7
+ * (bit 0 = +x, bit 1 = +y, bit 2 = +z) that stay inside the lattice.
+ * nerf_mesh_classify: edge_mask[p] = crossing bits of the owned edges (bit d-1), vert_count[p] = their number,
+ *   face_count[p] = triangles (0..12) of the cell whose low corner is p (0 on a high border).
+ * nerf_mesh_emit: vert_off / face_off = nerf_exclusive_scan_i32 of the two counts, V / F their totals.  Writes the
+ *   vertices lo + (i + t d) h, h = (hi - lo) / (n - 1), t = (f[p] - iso) / (f[p] - f[q]), ordered by (p, d); the
+ *   triangles (int32 vertex indices, normals towards lower density) ordered by (cell, tetrahedron, triangle); and,
+ *   when normals != NULL, -g / max(|g|, 1e-12) of the lattice's central-difference gradient (one-sided on the
+ *   border) interpolated along the edge.  lo / hi: HOST arrays of 3 floats, lo < hi.  V = F = 0 launches nothing.
+ *   No atomics: equal inputs give equal bits.  Zero-area triangles (a lattice value equal to iso) are kept. */
+int nerf_mesh_classify(const float* field, int nx, int ny, int nz, float iso, uint8_t* edge_mask,
+                       int32_t* vert_count, int32_t* face_count, hipStream_t stream);
+int nerf_mesh_emit(const float* field, int nx, int ny, int nz, float iso, const float* lo, const float* hi,
+                   const uint8_t* edge_mask, const int32_t* vert_off, const int32_t* face_off, int64_t V, int64_t F,
+                   float* verts, int32_t* faces, float* normals, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -4,5 +4,6 @@ Host side in Python/PyTorch-ROCm (device memory, streams, torch.distributed); ev
 hand-written HIP kernel in libnerf_amd.so reached through the C-ABI of include/nerf_amd.h.
 """
 from ._lib import LIB_PATH, lib  # noqa: F401
+from .mesh import Mesh, density_lattice, extract_mesh  # noqa: F401
 
-__all__ = ["LIB_PATH", "lib"]
+__all__ = ["LIB_PATH", "lib", "Mesh", "density_lattice", "extract_mesh"]

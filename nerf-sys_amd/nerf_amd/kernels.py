@@ -313,6 +313,54 @@ def image_metrics(pred, gt, color_space="linear", out=None, ws=None):
     return out
 
 
+# ------------------------------------------------------------------ mesh extraction
+
+
+def _box3(v, name):
+    v = [float(x) for x in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v)]
+    if len(v) != 3:
+        raise ValueError(f"{name} must hold 3 floats, got {len(v)}")
+    return v
+
+
+def mesh_extract(field, iso, lo, hi, normals=False):
+    """Marching tetrahedra (nerf_mesh_classify -> two scans -> nerf_mesh_emit): field (nx,ny,nz) float32, finite, every
+    dimension >= 2, sampled at lo + (ix,iy,iz) (hi - lo) / (n - 1); inside iff field > iso.  Returns verts (V,3)
+    float32 and faces (F,3) int32 (welded: one vertex per crossing lattice edge; face normals towards lower values),
+    and with ``normals`` the unit normals (V,3) of the lattice's central-difference gradient.  Two host reads: the
+    finiteness check and the two totals that size the outputs.  Bitwise reproducible (no atomics)."""
+    from .occupancy import exclusive_scan
+    need(field, "field")
+    if field.dim() != 3:
+        raise ValueError(f"field must be (nx,ny,nz), got {tuple(field.shape)}")
+    nx, ny, nz = (int(n) for n in field.shape)
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"every lattice dimension must be >= 2, got {(nx, ny, nz)}")
+    lo, hi = _box3(lo, "lo"), _box3(hi, "hi")
+    if not all(a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"lo must be below hi on every axis, got {lo} vs {hi}")
+    dev, P = field.device, nx * ny * nz
+    if 12 * P >= 2 ** 31:  # int32 scans of up to 12 triangles per cell (512^3 still fits)
+        raise ValueError(f"lattice too large: 12 * {P} points reaches 2^31")
+    if not bool(torch.isfinite(field).all()):
+        raise ValueError("field must be finite")
+    mask = torch.empty(P, dtype=torch.uint8, device=dev)
+    vcnt = torch.empty(P, dtype=torch.int32, device=dev)  # two allocations: the scan wants 16-byte aligned inputs
+    fcnt = torch.empty(P, dtype=torch.int32, device=dev)
+    check(lib().nerf_mesh_classify(ptr(field), nx, ny, nz, float(iso), ptr(mask), ptr(vcnt), ptr(fcnt), stream()),
+          "nerf_mesh_classify")
+    voff, foff = exclusive_scan(vcnt), exclusive_scan(fcnt)
+    V, F = (int(v) for v in torch.stack([voff[-1], foff[-1]]).tolist())
+    verts = torch.empty((V, 3), dtype=F32, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    nrm = torch.empty((V, 3), dtype=F32, device=dev) if normals else None
+    lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    check(lib().nerf_mesh_emit(ptr(field), nx, ny, nz, float(iso), lo_c, hi_c, ptr(mask), ptr(voff), ptr(foff), V, F,
+                               ptr(verts) if V else None, ptr(faces) if F else None,
+                               ptr(nrm) if normals and V else None, stream()), "nerf_mesh_emit")
+    return (verts, faces, nrm) if normals else (verts, faces)
+
+
 # ------------------------------------------------------------------ optimiser
 
 

@@ -774,6 +774,22 @@ class InstantNGP(nn.Module):
         g = self.density_grad(x, params)[1]
         return -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
 
+    def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
+                     chunk: int = 2 ** 20):
+        """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
+        (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
+        (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
+        lattice) or None."""
+        from .mesh import extract_mesh
+        if normals not in ("field", "grid", None):
+            raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
+        box = self._aabb_host if aabb is None else [float(v) for v in torch.as_tensor(aabb).reshape(-1).tolist()]
+        if len(box) != 6:
+            raise ValueError(f"aabb must hold 6 floats (min, max), got {len(box)}")
+        nrm = (lambda v: self.normals(v, params)) if normals == "field" else normals
+        return extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold, normals=nrm,
+                            chunk=chunk, device=self.xyz_encoder.hash_table.device)
+
     def _anneal_alpha_thre(self, step: int) -> None:
         if step < self.occ_warmup_steps:
             t = step / max(1, self.occ_warmup_steps - 1)

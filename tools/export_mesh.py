@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Export the surface of an Instant-NGP expert as a PLY (and optionally an OBJ): InstantNGP.extract_mesh, i.e. the
+density on a lattice over the scene box, then marching tetrahedra on the device.
+
+The expert is the production shape of tools/bench_ngp.py.  Its weights come from one of
+  --checkpoint FILE   a torch.save()d state_dict of the InstantNGP module (after NGPTrainer.sync_to_modules()), or
+  --train-steps N     N steps of NGPTrainer on the synthetic Blender-style scene (as tools/train_psnr.py builds it).
+With --save-checkpoint the trained state_dict is written for a later run.  Needs a GPU (no CPU fallback).
+
+  python tools/export_mesh.py --train-steps 2000 --resolution 256 --threshold 10 --out mesh.ply
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "nerf-sys_amd"))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+CONF = dict(hidden=64, sigma_depth=2, color_hidden=64, color_depth=2, dir_encoding="spherical",
+            hash_enc_conf=dict(levels=16, features_per_level=2, log2_hashmap_size=20, min_res=16, max_res=4096,
+                               interpolation="Linear"))
+AABB = [[-1.5, -1.5, -1.5], [1.5, 1.5, 1.5]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--checkpoint", help="state_dict of the InstantNGP module")
+    src.add_argument("--train-steps", type=int, help="train this many steps on the synthetic scene first")
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--samples", type=int, default=96)
+    ap.add_argument("--train-views", type=int, default=100)
+    ap.add_argument("--image-size", type=int, default=800)
+    ap.add_argument("--save-checkpoint", default=None)
+    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--threshold", type=float, default=10.0)
+    ap.add_argument("--normals", default="field", choices=["field", "grid", "none"])
+    ap.add_argument("--out", default="mesh.ply")
+    ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("export_mesh: needs a GPU (no CPU fallback)")
+    from nerf_amd.ngp import InstantNGP
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = InstantNGP(occ_conf={}, scene_box=torch.tensor(AABB), **CONF)
+    if a.checkpoint:
+        model.load_state_dict(torch.load(a.checkpoint, map_location="cpu"))
+        model = model.to(dev).eval()
+    else:
+        from nerf_amd.ngp_trainer import NGPTrainer
+        from nerf_amd.scene import make_blender_scene
+        from nerf_amd.trainer import RayBatcher
+        scene = make_blender_scene(n_train=a.train_views, n_test=1, H=a.image_size, W=a.image_size, seed=0, device=dev)
+        model = model.to(dev)
+        tr = NGPTrainer(model, n_samples=a.samples, device=dev)
+        rb = RayBatcher(scene, dev)
+        for step in range(a.train_steps):
+            rays, gt = rb.batch(a.batch, seed=step)
+            loss = tr.step(rays, gt, seed=step)
+        tr.sync_to_modules()
+        model.eval()
+        print(f"trained {a.train_steps} steps, loss {float(loss):.5f}" if a.train_steps else "untrained", file=sys.stderr)
+        if a.save_checkpoint:
+            torch.save(model.state_dict(), a.save_checkpoint)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mesh = model.extract_mesh(resolution=a.resolution, threshold=a.threshold,
+                              normals=None if a.normals == "none" else a.normals)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    mesh.save_ply(a.out)
+    if a.obj:
+        mesh.save_obj(a.obj)
+    print(json.dumps({"vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
+                      "resolution": a.resolution, "threshold": a.threshold, "normals": a.normals,
+                      "extract_seconds": round(dt, 4), "out": a.out}))
+
+
+if __name__ == "__main__":
+    main()
