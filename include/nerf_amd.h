@@ -654,6 +654,29 @@ int nerf_mesh_emit(const float* field, int nx, int ny, int nz, float iso, const 
                    const uint8_t* edge_mask, const int32_t* vert_off, const int32_t* face_off, int64_t V, int64_t F,
                    float* verts, int32_t* faces, float* normals, hipStream_t stream);
 
+/* Mesh clean-up.  faces (F,3) int32 with 0 <= index < V: ANY indexed triangle list (any vertex
+ * order, duplicated faces, repeated indices, unused vertices).  The kernels do not check the indices; the caller does.
+ * V < 2^31 and 3 F < 2^31 (else NERF_E_ARG).
+ * nerf_mesh_components: labels[v] = the smallest vertex index of v's connected component (two vertices are connected
+ *   iff a chain of faces joins them; an unused vertex is its own component) and face_count[l] = the faces of the
+ *   component labelled l (0 where l is no label); both (V) int32.  A lock-free union-find over labels itself
+ *   (parent[v] <= v at every instant), a flatten and a count: 4 launches, integer atomics only.  The outputs are a
+ *   function of the input alone, so equal inputs give equal bits.  status: 2 device int32; after the call status[0] != 0
+ *   iff a thread exhausted a loop bound (the outputs are then invalid) and status[1] = the most find steps one face
+ *   took.  F = 0 launches only the initialisation, V = 0 nothing.
+ * nerf_mesh_mark_used: keep32[f] = keep[f] != 0 (labels == NULL, keep (F) bytes) or keep[labels[faces[f][0]]] != 0
+ *   (keep (V) bytes, a flag per component label), and used[v] = 1 for every vertex of a kept face (used (V) int32,
+ *   zeroed by the caller).
+ * nerf_mesh_remap_faces: face_pos / vert_pos = nerf_exclusive_scan_i32 of keep32 / used, F_out the first total; kept
+ *   face f -> out row face_pos[f] = vert_pos of its three indices.  Kept faces and used vertices keep their order;
+ *   the vertex rows follow by nerf_flag_compact(used, vert_pos) and nerf_gather_rows. */
+int nerf_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* labels, int32_t* face_count,
+                         int32_t* status, hipStream_t stream);
+int nerf_mesh_mark_used(const int32_t* faces, const uint8_t* keep, const int32_t* labels, int64_t F, int64_t V,
+                        int32_t* keep32, int32_t* used, hipStream_t stream);
+int nerf_mesh_remap_faces(const int32_t* faces, const int32_t* keep32, const int32_t* face_pos, const int32_t* vert_pos,
+                          int64_t F, int64_t F_out, int32_t* out, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -151,6 +151,9 @@ def lib():
             "nerf_moe_blend_bwd": [P, I64, P, P, I, I, P, P, P, P, P],
             "nerf_mesh_classify": [P, I, I, I, F, P, P, P, P],
             "nerf_mesh_emit": [P, I, I, I, F, P, P, P, P, P, I64, I64, P, P, P, P],
+            "nerf_mesh_components": [P, I64, I64, P, P, P, P],
+            "nerf_mesh_mark_used": [P, P, P, I64, I64, P, P, P],
+            "nerf_mesh_remap_faces": [P, P, P, P, I64, I64, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -205,7 +208,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_packed_points_n", "nerf_pick_pixels_dseed", "nerf_adam_dstep", "nerf_occ_march_multi_staged_dseed",
            "nerf_image_metrics_tile", "nerf_image_metrics_workspace_bytes", "nerf_image_metrics",
            "nerf_hash_encode_bwd_x", "nerf_ngp_density_grad_workspace_bytes", "nerf_ngp_density_grad_enc",
-           "nerf_mesh_classify", "nerf_mesh_emit")
+           "nerf_mesh_classify", "nerf_mesh_emit", "nerf_mesh_components", "nerf_mesh_mark_used",
+           "nerf_mesh_remap_faces")
 
 
 def check(status: int, what: str) -> None:

@@ -361,6 +361,104 @@ def mesh_extract(field, iso, lo, hi, normals=False):
     return (verts, faces, nrm) if normals else (verts, faces)
 
 
+# ------------------------------------------------------------------ mesh clean-up
+
+
+def _faces_arg(faces, n_vertices, labels=None, ranges_checked=False):
+    """faces (F,3) int32, contiguous, on the device, 0 <= index < V, V and 3 F below 2^31 (and labels (V,) int32 in the
+    same range): ValueError before any launch (the kernels do not check).  The range check is one host read."""
+    need(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be (F,3), got {tuple(faces.shape)}")
+    V, F = int(n_vertices), int(faces.shape[0])
+    if V < 0 or V >= 2 ** 31 or 3 * F >= 2 ** 31:
+        raise ValueError(f"n_vertices and 3 * F must be in [0, 2^31), got V = {V}, F = {F}")
+    if labels is not None:
+        need(labels, "labels", torch.int32)
+        if tuple(labels.shape) != (V,):
+            raise ValueError(f"labels must be ({V},), got {tuple(labels.shape)}")
+    if F and not ranges_checked:
+        ranged =[faces] if labels is None else [faces, labels]
+        lim = torch.stack([t.min() for t in ranged] + [t.max() for t in ranged]).tolist()
+        if min(lim) < 0 or max(lim) >= V:
+            raise ValueError(f"face indices (and labels) must be in [0, {V}), got {min(lim)} .. {max(lim)}")
+    return V, F
+
+
+def mesh_components(faces, n_vertices, return_steps=False):
+    """Connected components of an indexed triangle list (nerf_mesh_components): faces (F,3) int32 with
+    0 <= index < n_vertices, any list (arbitrary order, duplicated faces, repeated indices, unused vertices).  Returns
+    labels (V,) int32, labels[v] = the smallest vertex index of v's component (an unused vertex is its own), and
+    face_count (V,) int32, face_count[l] = faces of the component labelled l (0 where l is no label).  Bitwise
+    reproducible: both are functions of the input alone.  Two host reads: the index range before the launches, the
+    status word after them (RuntimeError if a thread exhausted a loop bound; never silently wrong labels).  With
+    ``return_steps`` also the most find steps one face's unions took."""
+    V, F = _faces_arg(faces, n_vertices)
+    dev = faces.device
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    counts = torch.empty(V, dtype=torch.int32, device=dev)
+    if V == 0:  # nothing to launch, nothing to read
+        return (labels, counts, 0) if return_steps else (labels, counts)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    check(lib().nerf_mesh_components(ptr(faces) if F else None, F, V, ptr(labels), ptr(counts), ptr(status), stream()),
+          "nerf_mesh_components")
+    err, steps = status.tolist()
+    if err:
+        raise RuntimeError(f"nerf_mesh_components: a loop bound was exhausted (status {err}); the labels are invalid")
+    return (labels, counts, steps) if return_steps else (labels, counts)
+
+
+def mesh_compact(vertices, faces, keep_face, attrs=(), labels=None, ranges_checked=False):
+    """The mesh of the faces with keep_face != 0 (nerf_mesh_mark_used -> two scans -> nerf_mesh_remap_faces,
+    nerf_flag_compact, nerf_gather_rows): vertices (V,3) float32, faces (F,3) int32, keep_face (F,) uint8 or bool,
+    attrs a sequence of (V,C) float32.  Kept faces stay in their order; the vertices a kept face uses stay in their
+    order and are renumbered densely; every attribute is gathered like the vertices.  Returns (vertices, faces,
+    [attrs...]).  With ``labels`` (the (V,) int32 of mesh_components) keep_face is (V,), a flag per component label,
+    and face f is kept iff keep_face[labels[faces[f, 0]]].  Host reads: the index range (skipped with
+    ``ranges_checked``: these very faces and labels have just passed mesh_components), and the two totals that size
+    the outputs in one read."""
+    from .occupancy import exclusive_scan
+    need(vertices, "vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be (V,3), got {tuple(vertices.shape)}")
+    V, F = _faces_arg(faces, vertices.shape[0], labels, ranges_checked)
+    if not isinstance(keep_face, torch.Tensor) or keep_face.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("keep_face must be a uint8 or bool tensor")
+    keep_face = need(keep_face.view(torch.uint8) if keep_face.dtype == torch.bool else keep_face, "keep_face",
+                     torch.uint8)
+    n_keep = F if labels is None else V
+    if tuple(keep_face.shape) != (n_keep,):
+        raise ValueError(f"keep_face must be ({n_keep},), got {tuple(keep_face.shape)}")
+    attrs = list(attrs)
+    for i, a in enumerate(attrs):
+        need(a, f"attrs[{i}]")
+        if a.dim() != 2 or a.shape[0] != V or a.shape[1] < 1:
+            raise ValueError(f"attrs[{i}] must be ({V},C), got {tuple(a.shape)}")
+    dev = faces.device
+    if F == 0:
+        return (vertices.new_empty((0, 3)), faces.new_empty((0, 3)), [a.new_empty((0, a.shape[1])) for a in attrs])
+    keep32 = torch.empty(F, dtype=torch.int32, device=dev)
+    used = torch.zeros(V, dtype=torch.int32, device=dev)
+    check(lib().nerf_mesh_mark_used(ptr(faces), ptr(keep_face), ptr(labels), F, V, ptr(keep32), ptr(used), stream()),
+          "nerf_mesh_mark_used")
+    vpos, fpos = exclusive_scan(used), exclusive_scan(keep32)
+    Vo, Fo = (int(v) for v in torch.stack([vpos[-1], fpos[-1]]).tolist())
+    out_f = torch.empty((Fo, 3), dtype=torch.int32, device=dev)
+    check(lib().nerf_mesh_remap_faces(ptr(faces), ptr(keep32), ptr(fpos), ptr(vpos), F, Fo,
+                                      ptr(out_f) if Fo else None, stream()), "nerf_mesh_remap_faces")
+    vidx = torch.empty(Vo, dtype=torch.int32, device=dev)
+    if Vo:
+        check(lib().nerf_flag_compact(ptr(used), ptr(vpos), V, ptr(vidx), stream()), "nerf_flag_compact")
+
+    def rows(src):
+        dst = torch.empty((Vo, src.shape[1]), dtype=F32, device=dev)
+        check(lib().nerf_gather_rows(ptr(src), src.stride(0), ptr(vidx) if Vo else None, Vo, src.shape[1],
+                                     ptr(dst) if Vo else None, src.shape[1], stream()), "nerf_gather_rows")
+        return dst
+
+    return rows(vertices), out_f, [rows(a) for a in attrs]
+
+
 # ------------------------------------------------------------------ optimiser
 
 

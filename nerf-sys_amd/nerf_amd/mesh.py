@@ -5,6 +5,10 @@ The surface is the level set density = threshold; face and vertex normals point 
 of InstantNGP.normals.  Marching tetrahedra emits roughly 2-3 times the triangles of marching cubes at the same
 resolution, and a lattice value exactly on the threshold gives zero-area triangles; both are kept as they are (no
 simplification, no degenerate removal), so the connectivity is always closed inside the box.
+
+Clean-up on the device (csrc/mesh_clean.hip): Mesh.components labels the connected components,
+Mesh.filter_components keeps whole components by their number of faces (the small detached blobs of a trained density
+field go), Mesh.select_faces compacts to any subset of the faces; normals and colours ride along.
 """
 from __future__ import annotations
 
@@ -19,21 +23,26 @@ __all__ = ["Mesh", "density_lattice", "extract_mesh"]
 
 
 class Mesh:
-    """vertices (V,3) float32, faces (F,3) int32, optional per-vertex normals (V,3) float32; device or host tensors."""
+    """vertices (V,3) float32, faces (F,3) int32, optional per-vertex normals (V,3) float32 and colours (V,3) float32
+    in [0,1]; device or host tensors."""
 
-    def __init__(self, vertices, faces, normals=None):
+    def __init__(self, vertices, faces, normals=None, colors=None):
         if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
             raise ValueError(f"vertices (V,3) and faces (F,3) expected, got {tuple(vertices.shape)}, {tuple(faces.shape)}")
         if normals is not None and tuple(normals.shape) != tuple(vertices.shape):
             raise ValueError(f"normals must be {tuple(vertices.shape)}, got {tuple(normals.shape)}")
-        self.vertices, self.faces, self.normals = vertices, faces, normals
+        if colors is not None and tuple(colors.shape) != tuple(vertices.shape):
+            raise ValueError(f"colors must be {tuple(vertices.shape)}, got {tuple(colors.shape)}")
+        self.vertices, self.faces, self.normals, self.colors = vertices, faces, normals, colors
 
     def __repr__(self):
-        return (f"Mesh(V={self.vertices.shape[0]}, F={self.faces.shape[0]}, normals={self.normals is not None}, "
-                f"device={self.vertices.device})")
+        colors = "" if self.colors is None else ", colors=True"  # a mesh without colours prints as it always has
+        return (f"Mesh(V={self.vertices.shape[0]}, F={self.faces.shape[0]}, normals={self.normals is not None}"
+                f"{colors}, device={self.vertices.device})")
 
     def cpu(self) -> "Mesh":
-        return Mesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu())
+        return Mesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu(),
+                    None if self.colors is None else self.colors.cpu())
 
     def _host(self):
         v = self.vertices.detach().cpu().numpy().astype("<f4")
@@ -41,33 +50,102 @@ class Mesh:
         n = None if self.normals is None else self.normals.detach().cpu().numpy().astype("<f4")
         return v, f, n
 
+    def _host_colors(self):
+        return None if self.colors is None else self.colors.detach().cpu().numpy().astype("<f4")
+
     def save_ply(self, path) -> None:
-        """Binary little-endian PLY: float x y z [nx ny nz] per vertex, `list uchar int vertex_indices` per face."""
+        """Binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue = round(clamp(c,0,1) 255)] per
+        vertex, `list uchar int vertex_indices` per face."""
         v, f, n = self._host()
+        c = self._host_colors()
         props = ["x", "y", "z"] + (["nx", "ny", "nz"] if n is not None else [])
         header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
         header += [f"property float {p}" for p in props]
+        if c is not None:
+            header += [f"property uchar {p}" for p in ("red", "green", "blue")]
         header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
         rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
         rec["n"], rec["v"] = 3, f
+        xyz = np.ascontiguousarray(v if n is None else np.concatenate([v, n], 1))
         with open(path, "wb") as fh:
             fh.write(("\n".join(header) + "\n").encode("ascii"))
-            fh.write(np.ascontiguousarray(v if n is None else np.concatenate([v, n], 1)).tobytes())
+            if c is None:
+                fh.write(xyz.tobytes())
+            else:
+                vrec = np.empty(v.shape[0], dtype=[("f", "<f4", (xyz.shape[1],)), ("c", "u1", (3,))])
+                vrec["f"] = xyz
+                vrec["c"] = np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+                fh.write(vrec.tobytes())
             fh.write(rec.tobytes())
 
     def save_obj(self, path) -> None:
-        """Wavefront OBJ: v lines, vn lines when there are normals, 1-based f lines (a//a with normals); %.9g keeps
-        every float32 exactly."""
+        """Wavefront OBJ: v lines (`v x y z r g b` with colours, the common extension), vn lines when there are normals,
+        1-based f lines (a//a with normals); %.9g keeps every float32 exactly."""
         v, f, n = self._host()
+        c = self._host_colors()
         with open(path, "w") as fh:
-            for x in v.tolist():
-                fh.write("v %.9g %.9g %.9g\n" % tuple(x))
+            if c is None:
+                for x in v.tolist():
+                    fh.write("v %.9g %.9g %.9g\n" % tuple(x))
+            else:
+                for x in np.concatenate([v, c], 1).tolist():
+                    fh.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(x))
             if n is not None:
                 for x in n.tolist():
                     fh.write("vn %.9g %.9g %.9g\n" % tuple(x))
             fmt = "f %d//%d %d//%d %d//%d\n" if n is not None else "f %d %d %d\n"
-            for a, b, c in (f + 1).tolist():
-                fh.write(fmt % ((a, a, b, b, c, c) if n is not None else (a, b, c)))
+            for i, j, k in (f + 1).tolist():
+                fh.write(fmt % ((i, i, j, j, k, k) if n is not None else (i, j, k)))
+
+    # ---- clean-up on the device (kernels.mesh_components / mesh_compact, DESIGN §3.11.1)
+
+    def components(self):
+        """(labels (V,) int32, face_count (V,) int32): labels[v] = the smallest vertex index of v's connected
+        component, face_count[l] = the faces of the component labelled l (0 where l is no label)."""
+        return K.mesh_components(self.faces, self.vertices.shape[0])
+
+    def _compacted(self, keep, labels=None, ranges_checked=False) -> "Mesh":
+        attrs = [a for a in (self.normals, self.colors) if a is not None]
+        v, f, out = K.mesh_compact(self.vertices, self.faces, keep, attrs, labels=labels,
+                                   ranges_checked=ranges_checked)
+        out = iter(out)
+        return Mesh(v, f, None if self.normals is None else next(out), None if self.colors is None else next(out))
+
+    def select_faces(self, keep_face) -> "Mesh":
+        """The mesh of the faces with keep_face ((F,) bool or uint8) set: faces and used vertices keep their order,
+        the vertices are renumbered densely, normals and colours ride along."""
+        if not isinstance(keep_face, torch.Tensor) or tuple(keep_face.shape) != (self.faces.shape[0],):
+            raise ValueError(f"keep_face must be a ({self.faces.shape[0]},) tensor")
+        return self._compacted(keep_face)
+
+    def component_selection(self, min_faces=None, keep_largest=None):
+        """(labels, face_count, keep): keep (V,) bool is set at the labels of the components that
+        filter_components(min_faces, keep_largest) keeps.  The selection is a few torch ops on the device."""
+        if (min_faces is None) == (keep_largest is None):
+            raise ValueError("give exactly one of min_faces and keep_largest")
+        if int(min_faces if keep_largest is None else keep_largest) < 0:
+            raise ValueError("min_faces / keep_largest must be >= 0")
+        labels, count = self.components()
+        V = labels.shape[0]
+        is_label = labels == torch.arange(V, dtype=torch.int32, device=labels.device)
+        if min_faces is not None:
+            keep = is_label & (count >= int(min_faces))
+        else:
+            # a stable descending sort of the face counts over the vertices in ascending order, non-labels last: a tie
+            # goes to the smaller label
+            key = torch.where(is_label, count, torch.full_like(count, -1))
+            order = torch.sort(key, descending=True, stable=True).indices[:min(int(keep_largest), V)]
+            keep = torch.zeros(V, dtype=torch.bool, device=labels.device)
+            keep[order] = True
+            keep &= is_label
+        return labels, count, keep
+
+    def filter_components(self, min_faces=None, keep_largest=None) -> "Mesh":
+        """Keep whole connected components by their number of faces: every component with at least ``min_faces``, or
+        the ``keep_largest`` components with the most faces (a tie goes to the component with the smaller label; more
+        than there are keeps all).  Exactly one of the two is given."""
+        labels, _, keep = self.component_selection(min_faces, keep_largest)
+        return self._compacted(keep, labels=labels, ranges_checked=True)
 
 
 def _box(lo, hi):
@@ -111,18 +189,21 @@ def density_lattice(density_fn: Callable, lo, hi, resolution: Union[int, Sequenc
 
 
 def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[int]], threshold: float,
-                 normals: Union[str, None, Callable] = "grid", chunk: int = 2 ** 20, device=None) -> Mesh:
+                 normals: Union[str, None, Callable] = "grid", chunk: int = 2 ** 20, device=None,
+                 min_faces: Optional[int] = None, keep_largest: Optional[int] = None) -> Mesh:
     """The level set density_fn = threshold inside the box [lo, hi] as a Mesh on the device.  normals: "grid" (the
     lattice's central differences, from the extraction kernel), None, or a callable evaluated at the vertices
-    ((V,3) -> (V,3))."""
+    ((V,3) -> (V,3)).  min_faces / keep_largest (at most one): Mesh.filter_components on the extracted surface, before
+    a callable ``normals`` is evaluated, so that it runs on the surviving vertices only."""
     if not (normals is None or normals == "grid" or callable(normals)):
         raise ValueError(f"normals must be 'grid', None or a callable, got {normals!r}")
+    if min_faces is not None and keep_largest is not None:
+        raise ValueError("give at most one of min_faces and keep_largest")
     lo, hi = _box(lo, hi)
     field = density_lattice(density_fn, lo, hi, resolution, chunk=chunk, device=device)
-    if normals == "grid":
-        return Mesh(*K.mesh_extract(field, threshold, lo, hi, normals=True))
-    verts, faces = K.mesh_extract(field, threshold, lo, hi)
-    nrm: Optional[torch.Tensor] = None
+    mesh = Mesh(*K.mesh_extract(field, threshold, lo, hi, normals=(normals == "grid")))
+    if min_faces is not None or keep_largest is not None:
+        mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
     if callable(normals):
-        nrm = normals(verts) if verts.shape[0] else torch.empty_like(verts)
-    return Mesh(verts, faces, nrm)
+        mesh.normals = normals(mesh.vertices) if mesh.vertices.shape[0] else torch.empty_like(mesh.vertices)
+    return mesh

@@ -774,21 +774,58 @@ class InstantNGP(nn.Module):
         g = self.density_grad(x, params)[1]
         return -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
 
+    def vertex_colors(self, x: torch.Tensor, normals: torch.Tensor, params=None, chunk: int = 2 ** 20) -> torch.Tensor:
+        """Colours (M,3) in [0,1] of surface points x (M,3) with unit normals (M,3) that point to lower density: the
+        network's rgb for the view direction -normal, that of a ray arriving head-on from outside.  One fused launch
+        (encode + trunk + colour head) per chunk of ``chunk`` points, no graph; every row is evaluated on its own, so
+        the result does not depend on ``chunk``."""
+        if x.dim() != 2 or x.shape[1] != 3 or tuple(normals.shape) != tuple(x.shape):
+            raise ValueError(f"x and normals must both be (M,3), got {tuple(x.shape)}, {tuple(normals.shape)}")
+        if chunk < 1:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+        out = torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
+        with torch.no_grad():
+            for s in range(0, x.shape[0], chunk):
+                xd = torch.cat([x[s:s + chunk].float(), -normals[s:s + chunk].float()], -1)
+                rgb = self.forward(xd, params=params)[..., :3]
+                if not self.use_sigmoid_rgb:
+                    rgb = torch.sigmoid(rgb)
+                out[s:s + chunk] = rgb.clamp(0.0, 1.0)
+        return out
+
     def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
-                     chunk: int = 2 ** 20):
+                     chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None):
         """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
         (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
         (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
-        lattice) or None."""
+        lattice) or None.  colors: None, "linear" (self.vertex_colors along the field normals, which are computed for
+        the direction even when they are not stored) or "srgb" (losses.linear_to_srgb of them).  min_faces /
+        keep_largest (at most one): Mesh.filter_components, applied before field normals and colours are evaluated, so
+        the networks run on the surviving vertices only."""
         from .mesh import extract_mesh
         if normals not in ("field", "grid", None):
             raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
+        if colors not in (None, "linear", "srgb"):
+            raise ValueError(f"colors must be None, 'linear' or 'srgb', got {colors!r}")
         box = self._aabb_host if aabb is None else [float(v) for v in torch.as_tensor(aabb).reshape(-1).tolist()]
         if len(box) != 6:
             raise ValueError(f"aabb must hold 6 floats (min, max), got {len(box)}")
-        nrm = (lambda v: self.normals(v, params)) if normals == "field" else normals
-        return extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold, normals=nrm,
-                            chunk=chunk, device=self.xyz_encoder.hash_table.device)
+        mesh = extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold,
+                            normals="grid" if normals == "grid" else None, chunk=chunk,
+                            device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest)
+        v = mesh.vertices
+        field_nrm = None
+        if normals == "field" or colors is not None:
+            field_nrm = self.normals(v, params) if v.shape[0] else torch.empty_like(v)
+        if normals == "field":
+            mesh.normals = field_nrm
+        if colors is not None:
+            rgb = self.vertex_colors(v, field_nrm, params, chunk=chunk) if v.shape[0] else torch.empty_like(v)
+            if colors == "srgb":
+                from .losses import linear_to_srgb
+                rgb = linear_to_srgb(rgb)
+            mesh.colors = rgb
+        return mesh
 
     def _anneal_alpha_thre(self, step: int) -> None:
         if step < self.occ_warmup_steps:

@@ -8,6 +8,13 @@ The expert is the production shape of tools/bench_ngp.py.  Its weights come from
 With --save-checkpoint the trained state_dict is written for a later run.  Needs a GPU (no CPU fallback).
 
   python tools/export_mesh.py --train-steps 2000 --resolution 256 --threshold 10 --out mesh.ply
+
+--colors linear|srgb adds vertex colours (uchar red green blue in the PLY, `v x y z r g b` in the OBJ); --min-faces N
+or --keep-largest K removes the small detached components (floaters) on the device before normals and colours are
+evaluated.  The JSON line reports the number of components (those with a face) of the unfiltered
+surface and the faces before and after the filter.
+
+  python tools/export_mesh.py --train-steps 2000 --colors srgb --min-faces 200 --out mesh.ply
 """
 import argparse
 import json
@@ -40,6 +47,11 @@ def main():
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--threshold", type=float, default=10.0)
     ap.add_argument("--normals", default="field", choices=["field", "grid", "none"])
+    ap.add_argument("--colors", default="none", choices=["none", "linear", "srgb"],
+                    help="vertex colours from the colour network, seen head-on along the field normal")
+    flt = ap.add_mutually_exclusive_group()
+    flt.add_argument("--min-faces", type=int, default=None, help="drop connected components with fewer faces")
+    flt.add_argument("--keep-largest", type=int, default=None, help="keep the K components with the most faces")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -71,14 +83,23 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mesh = model.extract_mesh(resolution=a.resolution, threshold=a.threshold,
-                              normals=None if a.normals == "none" else a.normals)
+                              normals=None if a.normals == "none" else a.normals,
+                              colors=None if a.colors == "none" else a.colors,
+                              min_faces=a.min_faces, keep_largest=a.keep_largest)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mesh.save_ply(a.out)
     if a.obj:
         mesh.save_obj(a.obj)
+    # for the report only (outside the timed call): the unfiltered surface and its components
+    full = mesh if a.min_faces is None and a.keep_largest is None else model.extract_mesh(
+        resolution=a.resolution, threshold=a.threshold, normals=None)
+    n_components = int((full.components()[1] > 0).sum())
     print(json.dumps({"vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
                       "resolution": a.resolution, "threshold": a.threshold, "normals": a.normals,
+                      "colors": a.colors, "min_faces": a.min_faces, "keep_largest": a.keep_largest,
+                      "components": n_components, "faces_before_filter": int(full.faces.shape[0]),
+                      "faces_after_filter": int(mesh.faces.shape[0]),
                       "extract_seconds": round(dt, 4), "out": a.out}))
 
 
