@@ -677,6 +677,47 @@ int nerf_mesh_mark_used(const int32_t* faces, const uint8_t* keep, const int32_t
 int nerf_mesh_remap_faces(const int32_t* faces, const int32_t* keep32, const int32_t* face_pos, const int32_t* vert_pos,
                           int64_t F, int64_t F_out, int32_t* out, hipStream_t stream);
 
+/* Mesh simplification by vertex clustering.  The vertices are snapped to a uniform grid of cells
+ * lo + (ix,iy,iz) cell, dims = (nx,ny,nz) cells with every entry in [1, 2^20]; every occupied cell becomes one vertex.
+ * lo (3 floats) and dims (3 int32) are HOST arrays; cell > 0 and inv = 1 / cell, both fp32, the division done by the
+ * caller.  Per axis t = (v - lo) * inv (one fp32 subtract, one fp32 multiply), i = clamp(floorf(t), 0, dim - 1)
+ * clamped as a float, key = (ix ny + iy) nz + iz in int64: vertices outside the grid land in the border cells.  The
+ * vertices must be finite (the kernels do not check).  V < 2^31 and 3 F < 2^31, table_log2 in [0, 31] and
+ * 2^table_log2 > the number of items (V or F), else NERF_E_ARG; the workspace 16-byte aligned (else NERF_E_ALIGN) and
+ * of at least the bytes of the matching *_workspace_bytes function (else NERF_E_WORKSPACE), all before any launch.
+ * Integer atomics only, and every output is a function of the input alone, so equal inputs give equal bits.
+ * status: 2 device int32; after the call status[0] != 0 iff a thread exhausted its probe bound (2^table_log2 probes;
+ * the outputs are then invalid), status[1] = the longest probe chain a thread walked.
+ * nerf_mesh_cluster_labels: labels[v] (V) int32 = the smallest vertex index whose key equals v's.  A key pre-pass,
+ *   an insert into an open-addressing hash set of vertex indices (compare-and-swap on empty slots, atomicMin on the
+ *   slot of an equal key) and a lookup: 3 launches.  Workspace: the int64 keys and the 2^table_log2 int32 slots.
+ * nerf_mesh_cluster_reduce: the row of every representative (labels[v] == v) of out_vertices = the cell's corner plus
+ *   the mean cell-relative position of its members in 24-bit fixed point (uint64 sums), of out_normals (normals !=
+ *   NULL) = the normalised sum of the members' normals, clamped to [-1,1] and rounded to 2^-20 (int64 sums; a zero
+ *   sum gives zeros), of out_colors (colors != NULL) = the mean of the members' colours, clamped to [0,1] and rounded
+ *   to 2^-24; every other row zeros.  A NaN attribute counts as the lower bound of its clamp.  Init, accumulate
+ *   (64-bit integer atomicAdd at the row labels[v]) and finalize (double precision, every operation rounded on its
+ *   own): 3 launches.  Workspace: 3 (1 + normals + colours) uint64 and one int32 per vertex.
+ * nerf_mesh_cluster_faces: faces_out (F,3) = labels[faces] (still indices into the V input rows), keep[f] (F) uint8 =
+ *   1 iff the three new indices differ and f is the smallest face index among the faces with f's canonical form (the
+ *   rotation with the smallest index first; the cyclic order, hence the orientation, is kept: a face and its mirror
+ *   image are different forms).  A remap pass, an insert of the non-degenerate faces into a hash set of face indices
+ *   keyed by the canonical triple read through the index, and a lookup: 3 launches.  faces_out must not alias faces.
+ *   The result goes to nerf_mesh_mark_used / nerf_mesh_remap_faces with keep as the per-face flag. */
+int64_t nerf_mesh_cluster_labels_workspace_bytes(int64_t V, int table_log2);
+int nerf_mesh_cluster_labels(const float* vertices, int64_t V, const float* lo, float cell, float inv,
+                             const int32_t* dims, int table_log2, void* workspace, int64_t workspace_bytes,
+                             int32_t* labels, int32_t* status, hipStream_t stream);
+int64_t nerf_mesh_cluster_reduce_workspace_bytes(int64_t V, int has_normals, int has_colors);
+int nerf_mesh_cluster_reduce(const float* vertices, const int32_t* labels, const float* normals, const float* colors,
+                             int64_t V, const float* lo, float cell, float inv, const int32_t* dims, void* workspace,
+                             int64_t workspace_bytes, float* out_vertices, float* out_normals, float* out_colors,
+                             hipStream_t stream);
+int64_t nerf_mesh_cluster_faces_workspace_bytes(int64_t F, int table_log2);
+int nerf_mesh_cluster_faces(const int32_t* faces, const int32_t* labels, int64_t F, int64_t V, int table_log2,
+                            void* workspace, int64_t workspace_bytes, int32_t* faces_out, uint8_t* keep,
+                            int32_t* status, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

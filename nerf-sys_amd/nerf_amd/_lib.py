@@ -154,6 +154,12 @@ def lib():
             "nerf_mesh_components": [P, I64, I64, P, P, P, P],
             "nerf_mesh_mark_used": [P, P, P, I64, I64, P, P, P],
             "nerf_mesh_remap_faces": [P, P, P, P, I64, I64, P, P],
+            "nerf_mesh_cluster_labels_workspace_bytes": [I64, I],
+            "nerf_mesh_cluster_labels": [P, I64, P, F, F, P, I, P, I64, P, P, P],
+            "nerf_mesh_cluster_reduce_workspace_bytes": [I64, I, I],
+            "nerf_mesh_cluster_reduce": [P, P, P, P, I64, P, F, F, P, P, I64, P, P, P, P],
+            "nerf_mesh_cluster_faces_workspace_bytes": [I64, I],
+            "nerf_mesh_cluster_faces": [P, P, I64, I64, I, P, I64, P, P, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -180,6 +186,10 @@ def lib():
         L.nerf_occ_threshold_floats.restype = c_int64
         L.nerf_reptile_workspace_bytes.restype = c_int64
         L.nerf_image_metrics_workspace_bytes.restype = c_int64
+        for name in ("labels", "reduce", "faces"):
+            fn = getattr(L, f"nerf_mesh_cluster_{name}_workspace_bytes", None)  # absent from an older A/B library
+            if fn is not None:
+                fn.restype = c_int64
         _lib = L
     return _lib
 
@@ -209,7 +219,9 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_image_metrics_tile", "nerf_image_metrics_workspace_bytes", "nerf_image_metrics",
            "nerf_hash_encode_bwd_x", "nerf_ngp_density_grad_workspace_bytes", "nerf_ngp_density_grad_enc",
            "nerf_mesh_classify", "nerf_mesh_emit", "nerf_mesh_components", "nerf_mesh_mark_used",
-           "nerf_mesh_remap_faces")
+           "nerf_mesh_remap_faces", "nerf_mesh_cluster_labels_workspace_bytes", "nerf_mesh_cluster_labels",
+           "nerf_mesh_cluster_reduce_workspace_bytes", "nerf_mesh_cluster_reduce",
+           "nerf_mesh_cluster_faces_workspace_bytes", "nerf_mesh_cluster_faces")
 
 
 def check(status: int, what: str) -> None:

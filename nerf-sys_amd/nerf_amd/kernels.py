@@ -459,6 +459,137 @@ def mesh_compact(vertices, faces, keep_face, attrs=(), labels=None, ranges_check
     return rows(vertices), out_f, [rows(a) for a in attrs]
 
 
+# ------------------------------------------------------------------ mesh simplification
+
+
+def _table_log2(items, table_log2):
+    """The hash set's size: by default the smallest 2^k >= 2 * items, at least 2^6; a given k needs 2^k > items (one
+    slot always stays empty, which ends every probe chain)."""
+    if table_log2 is None:
+        return max(6, (2 * items - 1).bit_length())
+    k = int(table_log2)
+    if not 0 <= k <= 31 or (1 << k) <= items:
+        raise ValueError(f"table_log2 must be in [0, 31] with 2^table_log2 > {items}, got {table_log2}")
+    return k
+
+
+def _grid_arg(lo, cell, dims):
+    """(lo, cell, inv, dims) as the C-ABI takes them: cell > 0 rounded to fp32, inv = fp32(1) / fp32(cell)."""
+    import numpy as np
+    lo = _box3(lo, "lo")
+    with np.errstate(all="ignore"):
+        cell32 = np.float32(cell)
+        inv = np.float32(1.0) / cell32
+    if not (np.isfinite(cell32) and cell32 > 0 and np.isfinite(inv) and inv > 0):
+        raise ValueError(f"cell must be a finite positive float32 with a finite reciprocal, got {cell!r}")
+    dims = [int(d) for d in dims]
+    if len(dims) != 3 or min(dims) < 1 or max(dims) > 2 ** 20:
+        raise ValueError(f"dims must be 3 integers in [1, 2^20], got {dims}")
+    return (ctypes.c_float * 3)(*lo), float(cell32), float(inv), (ctypes.c_int32 * 3)(*dims)
+
+
+def _vertices_arg(vertices):
+    need(vertices, "vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices must be (V,3), got {tuple(vertices.shape)}")
+    V = int(vertices.shape[0])
+    if V >= 2 ** 31:
+        raise ValueError(f"V must be below 2^31, got {V}")
+    return V
+
+
+def _status(status, what):
+    err, probes = status.tolist()
+    if err:
+        raise RuntimeError(f"{what}: a probe bound was exhausted (status {err}); the result is invalid")
+    return probes
+
+
+def mesh_cluster_labels(vertices, lo, cell, dims, table_log2=None, return_probes=False):
+    """Vertex clustering, step 1 (nerf_mesh_cluster_labels): vertices (V,3) float32, finite; the grid of cells
+    lo + (ix,iy,iz) cell with dims = (nx,ny,nz) cells, each in [1, 2^20]; a vertex outside lands in a border cell.
+    Returns labels (V,) int32, labels[v] = the smallest vertex index in v's cell: a function of the input alone, so
+    bitwise reproducible.  table_log2: the hash set has 2^table_log2 slots (default: the smallest with
+    2^k >= 2 V, at least 6; a given value needs 2^k > V, else ValueError).  One host read, the status word
+    (RuntimeError if a thread exhausted its probe bound; never silently wrong labels).  With ``return_probes`` also
+    the longest probe chain."""
+    V = _vertices_arg(vertices)
+    lo_c, cell32, inv, dims_c = _grid_arg(lo, cell, dims)
+    k = _table_log2(V, table_log2)
+    dev = vertices.device
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    if V == 0:
+        return (labels, 0) if return_probes else labels
+    L = lib()
+    nb = int(L.nerf_mesh_cluster_labels_workspace_bytes(V, k))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    check(L.nerf_mesh_cluster_labels(ptr(vertices), V, lo_c, cell32, inv, dims_c, k, ptr(ws), nb, ptr(labels),
+                                     ptr(status), stream()), "nerf_mesh_cluster_labels")
+    probes = _status(status, "nerf_mesh_cluster_labels")
+    return (labels, probes) if return_probes else labels
+
+
+def mesh_cluster_reduce(vertices, labels, lo, cell, dims, normals=None, colors=None, ranges_checked=False):
+    """Vertex clustering, step 2 (nerf_mesh_cluster_reduce): one vertex per cluster, at the row of its representative
+    (labels[v] == v), every other row zeros.  Position: the cell's corner plus the mean of the members' cell-relative
+    positions in 24-bit fixed point; normals: the normalised sum of the members' (clamped to [-1,1], rounded to
+    2^-20; zeros when they cancel); colours: the mean of the members' (clamped to [0,1], rounded to 2^-24).  Integer
+    sums, so the result does not depend on the order of the atomics.  Returns (vertices, normals or None, colors or
+    None), each (V,3) float32.  One host read, the range of ``labels`` (skipped with ``ranges_checked``: these labels
+    have just come from mesh_cluster_labels)."""
+    V = _vertices_arg(vertices)
+    lo_c, cell32, inv, dims_c = _grid_arg(lo, cell, dims)
+    need(labels, "labels", torch.int32)
+    if tuple(labels.shape) != (V,):
+        raise ValueError(f"labels must be ({V},), got {tuple(labels.shape)}")
+    for a, name in ((normals, "normals"), (colors, "colors")):
+        if a is not None:
+            need(a, name)
+            if tuple(a.shape) != (V, 3):
+                raise ValueError(f"{name} must be ({V},3), got {tuple(a.shape)}")
+    if V and not ranges_checked:
+        a, b = torch.stack([labels.min(), labels.max()]).tolist()
+        if a < 0 or b >= V:
+            raise ValueError(f"labels must be in [0, {V}), got {a} .. {b}")
+    out = [torch.empty_like(vertices)] + [None if a is None else torch.empty_like(a) for a in (normals, colors)]
+    if V == 0:
+        return tuple(out)
+    L = lib()
+    nb = int(L.nerf_mesh_cluster_reduce_workspace_bytes(V, normals is not None, colors is not None))
+    ws = torch.empty(nb, dtype=torch.uint8, device=vertices.device)
+    check(L.nerf_mesh_cluster_reduce(ptr(vertices), ptr(labels), ptr(normals), ptr(colors), V, lo_c, cell32, inv,
+                                     dims_c, ptr(ws), nb, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream()),
+          "nerf_mesh_cluster_reduce")
+    return tuple(out)
+
+
+def mesh_cluster_faces(faces, labels, table_log2=None, return_probes=False, ranges_checked=False):
+    """Vertex clustering, step 3 (nerf_mesh_cluster_faces): faces (F,3) int32 and labels (V,) int32, both in [0, V).
+    Returns faces' (F,3) int32 = labels[faces] (still indices of the V input rows) and keep (F,) uint8: 1 iff the three
+    new indices differ and the face is the first (smallest face index) of its canonical form, the rotation with the
+    smallest index first; a face and its mirror image are different forms and are both kept.  mesh_compact(vertices of
+    mesh_cluster_reduce, faces', keep, attrs) then gives the simplified mesh.  table_log2 as in mesh_cluster_labels,
+    with F for V.  Two host reads: the index ranges (skipped with ``ranges_checked``) and the status word
+    (RuntimeError on an exhausted probe bound)."""
+    V, F = _faces_arg(faces, labels.shape[0] if isinstance(labels, torch.Tensor) and labels.dim() == 1 else -1, labels,
+                      ranges_checked)
+    k = _table_log2(F, table_log2)
+    dev = faces.device
+    out = torch.empty_like(faces)
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    if F == 0:
+        return (out, keep, 0) if return_probes else (out, keep)
+    L = lib()
+    nb = int(L.nerf_mesh_cluster_faces_workspace_bytes(F, k))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    check(L.nerf_mesh_cluster_faces(ptr(faces), ptr(labels), F, V, k, ptr(ws), nb, ptr(out), ptr(keep), ptr(status),
+                                    stream()), "nerf_mesh_cluster_faces")
+    probes = _status(status, "nerf_mesh_cluster_faces")
+    return (out, keep, probes) if return_probes else (out, keep)
+
+
 # ------------------------------------------------------------------ optimiser
 
 

@@ -15,6 +15,12 @@ evaluated.  The JSON line reports the number of components (th
 surface and the faces before and after the filter.
 
   python tools/export_mesh.py --train-steps 2000 --colors srgb --min-faces 200 --out mesh.ply
+
+--simplify CELL decimates the surface by vertex clustering on the device (Mesh.simplify): one vertex
+per occupied cell of edge CELL (world units), after the component filter and before normals and colours are evaluated.
+The JSON line then also reports the faces before the clustering.
+
+  python tools/export_mesh.py --train-steps 2000 --min-faces 200 --simplify 0.02 --out mesh.ply
 """
 import argparse
 import json
@@ -52,6 +58,8 @@ def main():
     flt = ap.add_mutually_exclusive_group()
     flt.add_argument("--min-faces", type=int, default=None, help="drop connected components with fewer faces")
     flt.add_argument("--keep-largest", type=int, default=None, help="keep the K components with the most faces")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                    help="vertex clustering with cells of this edge (world units)")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -85,21 +93,25 @@ def main():
     mesh = model.extract_mesh(resolution=a.resolution, threshold=a.threshold,
                               normals=None if a.normals == "none" else a.normals,
                               colors=None if a.colors == "none" else a.colors,
-                              min_faces=a.min_faces, keep_largest=a.keep_largest)
+                              min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mesh.save_ply(a.out)
     if a.obj:
         mesh.save_obj(a.obj)
     # for the report only (outside the timed call): the unfiltered surface and its components
-    full = mesh if a.min_faces is None and a.keep_largest is None else model.extract_mesh(
+    filtered = a.min_faces is not None or a.keep_largest is not None
+    full = mesh if not filtered and a.simplify is None else model.extract_mesh(
         resolution=a.resolution, threshold=a.threshold, normals=None)
     n_components = int((full.components()[1] > 0).sum())
+    after_filter = mesh if a.simplify is None else (
+        full.filter_components(min_faces=a.min_faces, keep_largest=a.keep_largest) if filtered else full)
     print(json.dumps({"vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]),
                       "resolution": a.resolution, "threshold": a.threshold, "normals": a.normals,
                       "colors": a.colors, "min_faces": a.min_faces, "keep_largest": a.keep_largest,
                       "components": n_components, "faces_before_filter": int(full.faces.shape[0]),
-                      "faces_after_filter": int(mesh.faces.shape[0]),
+                      "faces_after_filter": int(after_filter.faces.shape[0]), "simplify": a.simplify,
+                      "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
                       "extract_seconds": round(dt, 4), "out": a.out}))
 
 
