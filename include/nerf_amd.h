@@ -718,6 +718,41 @@ int nerf_mesh_cluster_faces(const int32_t* faces, const int32_t* labels, int64_t
                             void* workspace, int64_t workspace_bytes, int32_t* faces_out, uint8_t* keep,
                             int32_t* status, hipStream_t stream);
 
+/* Mesh smoothing: two CSR adjacencies built from sorted int64 keys, a Jacobi smoothing pass over the
+ * first and face-derived vertex normals over the second.  faces (F,3) int32 with 0 <= index < V: ANY indexed triangle
+ * list, as for the clean-up; the kernels do not check the indices or the finiteness of the vertices, the caller does.
+ * V < 2^31 and 6 F < 2^31 (the int32 scan of the flags), else NERF_E_ARG; the key arrays 8-byte aligned, else
+ * NERF_E_ALIGN; both before any launch.  No atomics: every output is a function of the input alone, so equal inputs
+ * give equal bits.  F = 0, n = 0 and V = 0 are empty calls (n = 0 with V > 0 zeroes row_off).
+ * A key is ((int64)row << 32) | (uint32)entry; INT64_MAX is the sentinel of a dropped pair.
+ * nerf_mesh_pair_keys: mode 0 writes the 6 F keys (a << 32) | b of the directed pairs (a,b) and (b,a) of every face's
+ *   three edges, in any order that is a function of the face index; a pair with a == b becomes the sentinel.  Mode 1
+ *   writes the 3 F keys (v << 32) | f of the corners.  The CALLER sorts the keys ascending (any int64 sort).
+ * nerf_mesh_csr_flags: flags[i] (n) int32 = sorted_keys[i] != sentinel && (i == 0 || sorted_keys[i] !=
+ *   sorted_keys[i-1]).  boundary (V) uint8, zeroed by the caller, or NULL: a plain store of 1 at the row of every
+ *   run of exactly one key (mode 0: a directed pair that occurs once, i.e. an edge used by exactly one face).
+ * nerf_mesh_csr_build: pos (n+1) = nerf_exclusive_scan_i32(flags), E = pos[n] read by the caller, who sizes col (E).
+ *   col[pos[i]] = the low 32 bits of sorted_keys[i] where flags[i] (positions >= E are not written), and
+ *   row_off[v] = pos[lower bound of v << 32 in sorted_keys] for v = 0..V (row_off (V+1), row_off[V] = E): a binary
+ *   search of at most 32 steps per vertex.  Row v of the result lists, ascending and once each, the vertices u != v
+ *   that share a face with v (mode 0) or the faces that contain v (mode 1); an unused vertex has an empty row.
+ * nerf_mesh_smooth_pass: v_out[v] = float(q + double(s) (m - q)) per axis, q = double(v_in[v]), m = the sum of
+ *   double(v_in[u]) over row v in the row's order divided by the row's length; every operation rounded on its own.
+ *   An empty row, fixed[v] != 0 (fixed (V) uint8 or NULL) and s == 0 copy v_in[v] bit for bit.  A Jacobi step: v_out
+ *   must not be v_in (NERF_E_ARG).  One thread per vertex.
+ * nerf_mesh_vertex_normals: normals_out[v] = g / max(|g|, 1e-12) in double, rounded to fp32, g = the sum over the
+ *   faces f of row v (the vertex-to-face adjacency), in the row's order, of (p[i1] - p[i0]) x (p[i2] - p[i0]) with
+ *   (i0,i1,i2) = faces[f]: area-weighted, by the face's winding; a zero sum (an unused vertex, faces that cancel)
+ *   gives zeros.  One thread per vertex. */
+int nerf_mesh_pair_keys(const int32_t* faces, int64_t F, int mode, int64_t* keys, hipStream_t stream);
+int nerf_mesh_csr_flags(const int64_t* sorted_keys, int64_t n, int32_t* flags, uint8_t* boundary, hipStream_t stream);
+int nerf_mesh_csr_build(const int64_t* sorted_keys, int64_t n, const int32_t* flags, const int32_t* pos, int64_t V,
+                        int64_t E, int32_t* row_off, int32_t* col, hipStream_t stream);
+int nerf_mesh_smooth_pass(const float* v_in, const int32_t* row_off, const int32_t* col, const uint8_t* fixed,
+                          int64_t V, float s, float* v_out, hipStream_t stream);
+int nerf_mesh_vertex_normals(const float* vertices, const int32_t* faces, const int32_t* row_off, const int32_t* col,
+                             int64_t V, float* normals_out, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

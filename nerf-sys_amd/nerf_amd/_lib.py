@@ -160,6 +160,11 @@ def lib():
             "nerf_mesh_cluster_reduce": [P, P, P, P, I64, P, F, F, P, P, I64, P, P, P, P],
             "nerf_mesh_cluster_faces_workspace_bytes": [I64, I],
             "nerf_mesh_cluster_faces": [P, P, I64, I64, I, P, I64, P, P, P, P],
+            "nerf_mesh_pair_keys": [P, I64, I, P, P],
+            "nerf_mesh_csr_flags": [P, I64, P, P, P],
+            "nerf_mesh_csr_build": [P, I64, P, P, I64, I64, P, P, P],
+            "nerf_mesh_smooth_pass": [P, P, P, P, I64, F, P, P],
+            "nerf_mesh_vertex_normals": [P, P, P, P, I64, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -221,7 +226,9 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_classify", "nerf_mesh_emit", "nerf_mesh_components", "nerf_mesh_mark_used",
            "nerf_mesh_remap_faces", "nerf_mesh_cluster_labels_workspace_bytes", "nerf_mesh_cluster_labels",
            "nerf_mesh_cluster_reduce_workspace_bytes", "nerf_mesh_cluster_reduce",
-           "nerf_mesh_cluster_faces_workspace_bytes", "nerf_mesh_cluster_faces")
+           "nerf_mesh_cluster_faces_workspace_bytes", "nerf_mesh_cluster_faces",
+           "nerf_mesh_pair_keys", "nerf_mesh_csr_flags", "nerf_mesh_csr_build", "nerf_mesh_smooth_pass",
+           "nerf_mesh_vertex_normals")
 
 
 def check(status: int, what: str) -> None:

@@ -590,6 +590,132 @@ def mesh_cluster_faces(faces, labels, table_log2=None, return_probes=False, rang
     return (out, keep, probes) if return_probes else (out, keep)
 
 
+# ------------------------------------------------------------------ mesh smoothing
+
+
+def _smooth_faces_arg(faces, n_vertices, ranges_checked=False):
+    """_faces_arg with the tighter size limit of the adjacency build: 6 F below 2^31 (the int32 scan of the flags)."""
+    if isinstance(faces, torch.Tensor) and faces.dim() == 2 and 6 * int(faces.shape[0]) >= 2 ** 31:
+        raise ValueError(f"6 * F must be below 2^31, got F = {int(faces.shape[0])}")
+    return _faces_arg(faces, n_vertices, ranges_checked=ranges_checked)
+
+
+def _csr(faces, V, F, mode, boundary=False):
+    """(row_off (V+1), col (E)[, boundary (V) uint8]) of the keys of ``mode``: nerf_mesh_pair_keys -> torch.sort ->
+    nerf_mesh_csr_flags -> the scan -> one host read of E -> nerf_mesh_csr_build."""
+    from .occupancy import exclusive_scan
+    dev = faces.device
+    n = (6 if mode == 0 else 3) * F
+    bnd = torch.zeros(V, dtype=torch.uint8, device=dev) if boundary else None
+    if n == 0:
+        out = (torch.zeros(V + 1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+        return out + (bnd,) if boundary else out
+    L = lib()
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    check(L.nerf_mesh_pair_keys(ptr(faces), F, mode, ptr(keys), stream()), "nerf_mesh_pair_keys")
+    keys = torch.sort(keys).values
+    flags = torch.empty(n, dtype=torch.int32, device=dev)
+    check(L.nerf_mesh_csr_flags(ptr(keys), n, ptr(flags), ptr(bnd) if boundary and V else None, stream()),
+          "nerf_mesh_csr_flags")
+    pos = exclusive_scan(flags)
+    E = int(pos[-1])
+    row_off = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(E, dtype=torch.int32, device=dev)
+    check(L.nerf_mesh_csr_build(ptr(keys), n, ptr(flags), ptr(pos), V, E, ptr(row_off), ptr(col) if E else None,
+                                stream()), "nerf_mesh_csr_build")
+    return (row_off, col, bnd) if boundary else (row_off, col)
+
+
+def mesh_adjacency(faces, n_vertices, boundary=False, ranges_checked=False):
+    """The vertex adjacency of an indexed triangle list as a CSR pair: faces (F,3) int32 with 0 <= index < n_vertices,
+    any list (duplicated faces, repeated indices, unused vertices), n_vertices and 6 F below 2^31.  Returns row_off
+    (V+1,) int32 and col (E,) int32: row v = col[row_off[v]:row_off[v+1]] lists, ascending and once each, the vertices
+    u != v that share a face with v (symmetric; an unused vertex has an empty row).  With ``boundary`` also (V,) uint8,
+    1 at the vertices of an edge that exactly one face uses (each face emits (a,b) and (b,a) for its three edges; a
+    vertex is marked iff one of its pairs occurs exactly once).  Sorted int64 keys (torch.sort), run flags, the
+    exclusive scan and a row build; no atomics, bitwise reproducible.  Two host reads: the index range (skipped with
+    ``ranges_checked``) and E."""
+    V, F = _smooth_faces_arg(faces, n_vertices, ranges_checked)
+    return _csr(faces, V, F, 0, boundary)
+
+
+def mesh_vertex_faces(faces, n_vertices, ranges_checked=False):
+    """The vertex-to-face adjacency in the same CSR form: row v lists, ascending and once each, the faces that contain
+    v (a face such as (a,a,b) is listed once for a).  Arguments and host reads as mesh_adjacency."""
+    V, F = _smooth_faces_arg(faces, n_vertices, ranges_checked)
+    return _csr(faces, V, F, 1)
+
+
+def _csr_arg(row_off, col, V, n_items, ranges_checked):
+    """row_off (V+1,) and col (E,) int32 on the device, and unless ``ranges_checked`` one host read: row_off starts at
+    0, never decreases and ends at E, col in [0, n_items)."""
+    need(row_off, "row_off", torch.int32)
+    need(col, "col", torch.int32)
+    if tuple(row_off.shape) != (V + 1,) or col.dim() != 1:
+        raise ValueError(f"row_off must be ({V + 1},) and col (E,), got {tuple(row_off.shape)}, {tuple(col.shape)}")
+    E = int(col.shape[0])
+    if not ranges_checked:
+        steps = (row_off[1:] - row_off[:-1]).min() if V else row_off[0] * 0
+        lim = [row_off[0], row_off[-1], steps] + ([col.min(), col.max()] if E else [])
+        lim = torch.stack([t.to(torch.int64) for t in lim]).tolist()
+        if lim[0] != 0 or lim[1] != E or lim[2] < 0:
+            raise ValueError(f"row_off must rise from 0 to len(col) = {E}")
+        if E and (lim[3] < 0 or lim[4] >= n_items):
+            raise ValueError(f"col must be in [0, {n_items}), got {lim[3]} .. {lim[4]}")
+    return E
+
+
+def mesh_smooth_pass(vertices, row_off, col, s, fixed=None, out=None, ranges_checked=False):
+    """One Jacobi smoothing step (nerf_mesh_smooth_pass): vertices (V,3) float32, finite; (row_off, col) of
+    mesh_adjacency; s a float32 factor; fixed None or (V,) uint8 / bool.  out[v] = float(q + double(s) (m - q)) per
+    axis with q = double(vertices[v]) and m the mean, in double and in the row's order, of the row's vertices; a vertex
+    with an empty row, a fixed one and s == 0 keep their bits.  ``out``: a (V,3) float32 buffer that does not share
+    memory with ``vertices`` (default: a new one).  One host read, the ranges of the adjacency (skipped with
+    ``ranges_checked``: it has just come from mesh_adjacency for this vertex count)."""
+    import numpy as np
+    V = _vertices_arg(vertices)
+    _csr_arg(row_off, col, V, V, ranges_checked)
+    with np.errstate(all="ignore"):
+        s32 = np.float32(s)
+    if not np.isfinite(s32):
+        raise ValueError(f"s must be a finite float32, got {s!r}")
+    if fixed is not None:
+        if not isinstance(fixed, torch.Tensor) or fixed.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("fixed must be a uint8 or bool tensor")
+        fixed = need(fixed.view(torch.uint8) if fixed.dtype == torch.bool else fixed, "fixed", torch.uint8)
+        if tuple(fixed.shape) != (V,):
+            raise ValueError(f"fixed must be ({V},), got {tuple(fixed.shape)}")
+    if out is None:
+        out = torch.empty_like(vertices)
+    else:
+        need(out, "out")
+        if tuple(out.shape) != (V, 3):
+            raise ValueError(f"out must be ({V},3), got {tuple(out.shape)}")
+        if V and abs(out.data_ptr() - vertices.data_ptr()) < 12 * V:
+            raise ValueError("out must not share memory with vertices (a Jacobi step reads every old position)")
+    if V:
+        check(lib().nerf_mesh_smooth_pass(ptr(vertices), ptr(row_off), ptr(col) if col.numel() else None, ptr(fixed),
+                                          V, float(s32), ptr(out), stream()), "nerf_mesh_smooth_pass")
+    return out
+
+
+def mesh_vertex_normals(vertices, faces, row_off, col, ranges_checked=False):
+    """Unit vertex normals from the faces (nerf_mesh_vertex_normals): vertices (V,3) float32, finite; faces (F,3)
+    int32; (row_off, col) of mesh_vertex_faces.  normal[v] = g / max(|g|, 1e-12), g = the sum in double, in the row's
+    order, of (p[i1] - p[i0]) x (p[i2] - p[i0]) over the faces of v: area-weighted, by the faces' winding (the
+    extractor's winding points to lower density); zeros at an unused vertex and where the faces cancel.  Host reads:
+    the index ranges of the faces and of the adjacency (skipped with ``ranges_checked``)."""
+    V = _vertices_arg(vertices)
+    _, F = _smooth_faces_arg(faces, V, ranges_checked)
+    _csr_arg(row_off, col, V, F, ranges_checked)
+    out = torch.empty_like(vertices)
+    if V:
+        check(lib().nerf_mesh_vertex_normals(ptr(vertices), ptr(faces) if F else None, ptr(row_off),
+                                             ptr(col) if col.numel() else None, V, ptr(out), stream()),
+              "nerf_mesh_vertex_normals")
+    return out
+
+
 # ------------------------------------------------------------------ optimiser
 
 

@@ -13,6 +13,10 @@ field go), Mesh.select_faces compacts to any subset of the faces; normals and co
 Simplification on the device (csrc/mesh_simplify.hip): Mesh.simplify clusters the vertices on a grid
 of cells (one vertex per occupied cell, collapsed and duplicated faces dropped); a tiny cell welds coincident vertices
 and removes the zero-area triangles.
+
+Smoothing on the device (csrc/mesh_smooth.hip): Mesh.smooth runs Taubin (or plain Laplacian) passes
+over a CSR vertex adjacency built once, with open boundaries held fixed by default; Mesh.compute_normals derives
+area-weighted vertex normals from the faces.
 """
 from __future__ import annotations
 
@@ -198,6 +202,82 @@ class Mesh:
         out = iter(out)
         return Mesh(ov, of, None if cn is None else next(out), None if cc is None else next(out))
 
+    # ---- smoothing on the device (kernels.mesh_adjacency / mesh_smooth_pass / mesh_vertex_normals)
+
+    def adjacency(self):
+        """(row_off (V+1,) int32, col (E,) int32): row v = col[row_off[v]:row_off[v+1]] lists, ascending and once
+        each, the vertices that share a face with v."""
+        return K.mesh_adjacency(self.faces, self.vertices.shape[0])
+
+    def boundary_vertices(self) -> torch.Tensor:
+        """(V,) bool: the vertices of an edge that exactly one face uses.  A closed surface has none."""
+        return K.mesh_adjacency(self.faces, self.vertices.shape[0], boundary=True)[2].to(torch.bool)
+
+    def _face_normals(self, vertices, ranges_checked=False):
+        row_off, col = K.mesh_vertex_faces(self.faces, vertices.shape[0], ranges_checked=ranges_checked)
+        return K.mesh_vertex_normals(vertices, self.faces, row_off, col, ranges_checked=True)
+
+    def compute_normals(self) -> "Mesh":
+        """The mesh with unit vertex normals derived from its faces: the normalised sum of the cross products of the
+        faces around a vertex (area-weighted), by the faces' winding, which for an extracted mesh points to lower
+        density like every normal here; zeros at a vertex without a face.  Vertices, faces and colours are the same
+        tensors."""
+        K._vertices_arg(self.vertices)
+        return Mesh(self.vertices, self.faces, self._face_normals(self.vertices), self.colors)
+
+    def smooth(self, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, fixed=None) -> "Mesh":
+        """Taubin smoothing: ``iterations`` times a Jacobi pass v += lam (mean of the neighbours - v) followed by one
+        with ``mu`` < -lam, which undoes the shrinkage of the first; ``mu=None`` gives plain Laplacian smoothing, one
+        pass per iteration.  The neighbours are the vertices that share a face (uniform weights); the adjacency is
+        built once.  ``fixed``: a (V,) bool or uint8 mask of vertices that do not move; with ``fix_boundary`` the
+        vertices of open edges (boundary_vertices) are added to it.  Faces and colours are returned unchanged, the
+        vertex count and order too; normals, if the mesh has them, are replaced by those of compute_normals on the
+        result.  ``iterations == 0`` returns the mesh's data unchanged.  Bitwise reproducible.  ValueError before any
+        launch on ``iterations`` that is no int >= 0, ``lam`` no finite float32 in (0, 1], ``mu`` neither None nor a
+        finite float32 below -lam, a ``fixed`` of the wrong shape or dtype, non-finite vertices, 6 F >= 2^31."""
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+            raise ValueError(f"iterations must be an int >= 0, got {iterations!r}")
+        with np.errstate(all="ignore"):
+            try:
+                lam32 = np.float32(lam)
+                mu32 = None if mu is None else np.float32(mu)
+            except (TypeError, ValueError):
+                raise ValueError(f"lam and mu must be floats, got {lam!r}, {mu!r}") from None
+        if not (np.isfinite(lam32) and 0 < lam32 <= 1):
+            raise ValueError(f"lam must be a finite float32 in (0, 1], got {lam!r}")
+        if mu32 is not None and not (np.isfinite(mu32) and mu32 < -lam32):
+            raise ValueError(f"mu must be None or a finite float32 below -lam = {-lam32}, got {mu!r}")
+        v, f = self.vertices, self.faces
+        V, F = int(v.shape[0]), int(f.shape[0])
+        if fixed is not None:
+            if (not isinstance(fixed, torch.Tensor) or fixed.dtype not in (torch.bool, torch.uint8)
+                    or tuple(fixed.shape) != (V,)):
+                raise ValueError(f"fixed must be a ({V},) bool or uint8 tensor")
+        if 6 * F >= 2 ** 31:
+            raise ValueError(f"6 * F must be below 2^31, got F = {F}")
+        if iterations == 0 or V == 0 or F == 0:
+            return Mesh(v, f, self.normals, self.colors)
+        K._vertices_arg(v)
+        K._faces_arg(f, V)  # the index range, before anything is launched on these faces
+        if fixed is not None:
+            fixed = K.need(fixed.view(torch.uint8) if fixed.dtype == torch.bool else fixed, "fixed", torch.uint8)
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("vertices must be finite")
+        if fix_boundary:
+            row_off, col, boundary = K.mesh_adjacency(f, V, boundary=True, ranges_checked=True)
+            fixed = boundary if fixed is None else (fixed != 0).to(torch.uint8) | boundary
+        else:
+            row_off, col = K.mesh_adjacency(f, V, ranges_checked=True)
+        cur, bufs, i = v, [None, None], 0  # two buffers swapped between the passes; the input is never written
+        for _ in range(int(iterations)):
+            for s in (lam32,) if mu32 is None else (lam32, mu32):
+                if bufs[i] is None:
+                    bufs[i] = torch.empty_like(v)
+                cur = K.mesh_smooth_pass(cur, row_off, col, s, fixed=fixed, out=bufs[i], ranges_checked=True)
+                i ^= 1
+        normals = None if self.normals is None else self._face_normals(cur, ranges_checked=True)
+        return Mesh(cur, f, normals, self.colors)
+
 
 def _box(lo, hi):
     lo = [float(x) for x in (lo.reshape(-1).tolist() if isinstance(lo, torch.Tensor) else lo)]
@@ -242,15 +322,19 @@ def density_lattice(density_fn: Callable, lo, hi, resolution: Union[int, Sequenc
 def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[int]], threshold: float,
                  normals: Union[str, None, Callable] = "grid", chunk: int = 2 ** 20, device=None,
                  min_faces: Optional[int] = None, keep_largest: Optional[int] = None,
-                 simplify: Optional[float] = None) -> Mesh:
+                 simplify: Optional[float] = None, smooth: Optional[int] = None) -> Mesh:
     """The level set density_fn = threshold inside the box [lo, hi] as a Mesh on the device.  normals: "grid" (the
     lattice's central differences, from the extraction kernel), None, or a callable evaluated at the vertices
     ((V,3) -> (V,3)).  min_faces / keep_largest (at most one): Mesh.filter_components on the extracted surface, before
     a callable ``normals`` is evaluated, so that it runs on the surviving vertices only.  simplify: a cell size in
     world units for Mesh.simplify, applied after the component filter and also before a callable ``normals``; "grid"
-    normals are averaged per cell by the clustering kernel."""
+    normals are averaged per cell by the clustering kernel.  smooth: a number of Taubin iterations for Mesh.smooth with
+    its defaults, applied after ``simplify`` and also before a callable ``normals``; "grid" normals are then replaced
+    by the face-derived normals of the smoothed mesh (Mesh.compute_normals).  None returns the surface unsmoothed."""
     if not (normals is None or normals == "grid" or callable(normals)):
         raise ValueError(f"normals must be 'grid', None or a callable, got {normals!r}")
+    if smooth is not None and (isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0):
+        raise ValueError(f"smooth must be None or an int >= 0, got {smooth!r}")
     if min_faces is not None and keep_largest is not None:
         raise ValueError("give at most one of min_faces and keep_largest")
     lo, hi = _box(lo, hi)
@@ -260,6 +344,8 @@ def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[i
         mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
     if simplify is not None:
         mesh = mesh.simplify(simplify)
+    if smooth is not None:
+        mesh = mesh.smooth(smooth)
     if callable(normals):
         mesh.normals = normals(mesh.vertices) if mesh.vertices.shape[0] else torch.empty_like(mesh.vertices)
     return mesh

@@ -794,7 +794,8 @@ class InstantNGP(nn.Module):
         return out
 
     def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
-                     chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None, simplify=None):
+                     chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None, simplify=None,
+                     smooth=None):
         """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
         (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
         (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
@@ -802,7 +803,9 @@ class InstantNGP(nn.Module):
         the direction even when they are not stored) or "srgb" (losses.linear_to_srgb of them).  min_faces /
         keep_largest (at most one): Mesh.filter_components, applied before field normals and colours are evaluated, so
         the networks run on the surviving vertices only.  simplify: a cell size in world units for Mesh.simplify
-        (vertex clustering), applied after that filter and likewise before field normals and colours."""
+        (vertex clustering), applied after that filter and likewise before field normals and colours.  smooth: a
+        number of Taubin iterations for Mesh.smooth, applied after ``simplify``: field normals and colours are then
+        evaluated at the smoothed vertices, and "grid" normals become the face-derived normals of the smoothed mesh."""
         from .mesh import extract_mesh
         if normals not in ("field", "grid", None):
             raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
@@ -814,7 +817,7 @@ class InstantNGP(nn.Module):
         mesh = extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold,
                             normals="grid" if normals == "grid" else None, chunk=chunk,
                             device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest,
-                            simplify=simplify)
+                            simplify=simplify, smooth=smooth)
         v = mesh.vertices
         field_nrm = None
         if normals == "field" or colors is not None:

@@ -21,6 +21,11 @@ per occupied cell of edge CELL (world units), after the component filter and bef
 The JSON line then also reports the faces before the clustering.
 
   python tools/export_mesh.py --train-steps 2000 --min-faces 200 --simplify 0.02 --out mesh.ply
+
+--smooth N runs N Taubin iterations on the device (Mesh.smooth) after the filter and the clustering and
+before normals and colours are evaluated; "grid" normals become the face-derived normals of the smoothed surface.
+
+  python tools/export_mesh.py --train-steps 2000 --min-faces 200 --smooth 10 --out mesh.ply
 """
 import argparse
 import json
@@ -60,6 +65,7 @@ def main():
     flt.add_argument("--keep-largest", type=int, default=None, help="keep the K components with the most faces")
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
                     help="vertex clustering with cells of this edge (world units)")
+    ap.add_argument("--smooth", type=int, default=None, metavar="N", help="Taubin smoothing iterations")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -93,7 +99,8 @@ def main():
     mesh = model.extract_mesh(resolution=a.resolution, threshold=a.threshold,
                               normals=None if a.normals == "none" else a.normals,
                               colors=None if a.colors == "none" else a.colors,
-                              min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify)
+                              min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify,
+                              smooth=a.smooth)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mesh.save_ply(a.out)
@@ -111,6 +118,7 @@ def main():
                       "colors": a.colors, "min_faces": a.min_faces, "keep_largest": a.keep_largest,
                       "components": n_components, "faces_before_filter": int(full.faces.shape[0]),
                       "faces_after_filter": int(after_filter.faces.shape[0]), "simplify": a.simplify,
+                      "smooth": a.smooth,
                       "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
                       "extract_seconds": round(dt, 4), "out": a.out}))
 
