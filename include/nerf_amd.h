@@ -753,6 +753,46 @@ int nerf_mesh_smooth_pass(const float* v_in, const int32_t* row_off, const int32
 int nerf_mesh_vertex_normals(const float* vertices, const int32_t* faces, const int32_t* row_off, const int32_t* col,
                              int64_t V, float* normals_out, hipStream_t stream);
 
+/* Mesh metrics: area-weighted surface samples and the exact nearest neighbour of every point of one
+ * set in another, the two device stages of Chamfer / Hausdorff / F-score.  vertices (V,3) float32 finite, faces (F,3)
+ * int32 with 0 <= index < V, points (.,3) float32 finite: the kernels check neither the indices nor the finiteness,
+ * the caller does.  3 F, n and m below 2^31, total in (0, 2^63), every dim in [1, 1024], cell and inv finite and
+ * positive, else NERF_E_ARG; the double, int64 key and cdf arrays 8-byte aligned, else NERF_E_ALIGN; both before any
+ * launch.  No LDS, no atomics: every output is a function of the input alone, so equal inputs give equal bits.
+ * F = 0 (areas), n = 0 and m = 0 (keys) are empty calls.  Every fp32 and fp64 operation named below rounds on its own.
+ * nerf_mesh_face_areas: area[f] (F) double = 0.5 sqrt((x x + y y) + z z) of (p1 - p0) x (p2 - p0), the corners
+ *   converted to double first; exactly 0 for a face with a repeated index.  One thread per face.
+ * nerf_mesh_sample_surface: cdf (F) int64 = the CALLER's inclusive sum of non-negative integer face weights and
+ *   total = cdf[F-1] (kernels.mesh_sample_surface: weights rint(area 2^e) with the largest in [2^31, 2^32]).  Sample
+ *   i draws z_k = mix64(seed 0x9e3779b97f4a7c15 + mix64((0x6d657368 + k) 0xd1b54a32d192ed03 + i)), k = 0, 1, 2 (the
+ *   64-bit value behind the project's counter RNG).  Face f = the first with cdf[f] > umulhi64(z_0, total), a binary
+ *   search of at most 32 steps: a face of weight 0 is never chosen.  k1 = z_1 >> 40, k2 = z_2 >> 40, both replaced by
+ *   2^24 - k when k1 + k2 > 2^24, u = k 2^-24; points[i] = float((p0 + u1 (p1 - p0)) + u2 (p2 - p0)) per axis in
+ *   double, face_idx[i] = f.  normals_out (n,3) or NULL: with vertex_normals == NULL the face's cross product divided
+ *   by its length, in double, rounded once; with vertex_normals (V,3) g / max(|g|, 1e-12) of
+ *   g = ((1 - u1 - u2) n0 + u1 n1) + u2 n2.  vertex_normals without normals_out is NERF_E_ARG.  One thread per sample.
+ * nerf_points_cell_keys: keys[j] (m) int64 = (cell_id << 32) | j, cell_id = (ix ny + iy) nz + iz < 2^30 with the fp32
+ *   cell index of nerf_mesh_cluster_labels: t = (p - lo) * inv, i = clamp(floorf(t), 0, dim - 1).  lo (3 floats) and
+ *   dims (3 int32) are HOST arrays, inv = 1 / cell in fp32, the division done by the caller.  The CALLER sorts the keys
+ *   ascending (any int64 sort) and gathers the points in key order (nerf_gather_rows over the low words).
+ * nerf_points_nearest: for every query (n,3) the nearest of the m reference points behind sorted_keys (m) and
+ *   sorted_points (m,3): d2[i] = (dx dx + dy dy) + dz dz in fp32, the smallest over the points, idx[i] = the original
+ *   index (the key's low word) of that point, the smallest such index on equal d2: brute force's result bit for bit.
+ *   Every reference point must lie in the box [lo, lo + dims cell] (up to rounding); a query may lie anywhere.  The
+ *   search walks the Chebyshev shells r = 0, 1, .. < max(dims) around the query's clamped cell, per (ix, iy) column
+ *   one lower bound over the keys and a walk over the column's run, and stops before shell r >= 2 once
+ *   best_d2 <= ((r - 1 - 2^-8) cell)^2 (1 - 2^-10) (the slack: mesh_metrics_core.hpp).  m = 0: d2 = +inf, idx = -1.
+ *   One thread per query; queries presented in the order of their own cell keys keep a wave on the same columns. */
+int nerf_mesh_face_areas(const float* vertices, const int32_t* faces, int64_t F, double* area, hipStream_t stream);
+int nerf_mesh_sample_surface(const float* vertices, const int32_t* faces, int64_t F, const int64_t* cdf,
+                             uint64_t total, const float* vertex_normals, int64_t n, uint64_t seed, float* points,
+                             int32_t* face_idx, float* normals_out, hipStream_t stream);
+int nerf_points_cell_keys(const float* points, int64_t m, const float* lo, float inv, const int32_t* dims,
+                          int64_t* keys, hipStream_t stream);
+int nerf_points_nearest(const float* query, int64_t n, const int64_t* sorted_keys, const float* sorted_points,
+                        int64_t m, const float* lo, float cell, float inv, const int32_t* dims, float* d2,
+                        int32_t* idx, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

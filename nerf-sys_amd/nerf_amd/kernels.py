@@ -716,6 +716,222 @@ def mesh_vertex_normals(vertices, faces, row_off, col, ranges_checked=False):
     return out
 
 
+# ------------------------------------------------------------------ mesh metrics
+
+
+def _finite_vertices(vertices):
+    V = _vertices_arg(vertices)
+    if V and not bool(torch.isfinite(vertices).all()):
+        raise ValueError("vertices must be finite")
+    return V
+
+
+def mesh_face_areas(vertices, faces, ranges_checked=False):
+    """The area of every face (nerf_mesh_face_areas): vertices (V,3) float32, finite; faces (F,3) int32.  Returns (F,)
+    float64: 0.5 |(p1 - p0) x (p2 - p0)| with every operation in double and rounded on its own; a face with a repeated
+    index has area exactly 0.  Bitwise reproducible.  Host reads: the finiteness of the vertices and the index range
+    (both skipped with ``ranges_checked``)."""
+    V = _vertices_arg(vertices) if ranges_checked else _finite_vertices(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=ranges_checked)
+    area = torch.empty(F, dtype=torch.float64, device=faces.device)
+    if F:
+        check(lib().nerf_mesh_face_areas(ptr(vertices), ptr(faces), F, ptr(area), stream()), "nerf_mesh_face_areas")
+    return area
+
+
+def mesh_area_cdf(area):
+    """The integer CDF of the sampler, exact in any order of evaluation: area (F,) float64 >= 0 ->
+    (cdf (F,) int64, total int).  e = 32 - frexp(max area).exponent, weight = rint(area 2^e) (the largest weight lies in
+    [2^31, 2^32], a face more than 2^32 times smaller than the largest gets weight 0), cdf = the inclusive sum,
+    total = cdf[-1] < 2^63 for F < 2^31.  Two host reads: the largest area (the power of two is then an exact host
+    float, whatever the device's pow does) and total.  F == 0 and an all-zero area give total 0."""
+    import math
+    if area.numel() == 0:
+        return torch.empty(0, dtype=torch.int64, device=area.device), 0
+    amax = float(area.max())
+    if not amax > 0.0:
+        return torch.zeros(area.shape[0], dtype=torch.int64, device=area.device), 0
+    scale = math.ldexp(1.0, 32 - math.frexp(amax)[1])
+    cdf = torch.cumsum(torch.round(area * scale).to(torch.int64), 0)
+    return cdf, int(cdf[-1])
+
+
+def _count_arg(n, name="n"):
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0 or n >= 2 ** 31:
+        raise ValueError(f"{name} must be an int in [0, 2^31), got {n!r}")
+    return n
+
+
+def _seed_arg(seed):
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+    return seed
+
+
+def mesh_sample_surface(vertices, faces, n, seed=0, normals=None, vertex_normals=None):
+    """n points distributed uniformly by area over the faces (nerf_mesh_face_areas -> mesh_area_cdf ->
+    nerf_mesh_sample_surface): vertices (V,3) float32, finite; faces (F,3) int32; n an int in [0, 2^31); seed an int in
+    [0, 2^64).  Returns (points (n,3) float32, face_idx (n,) int32) and, with ``normals`` = "face" or "vertex", unit
+    normals (n,3) float32: the face's own by its winding, or the barycentric mix of ``vertex_normals`` (V,3),
+    normalised.  Sample i is a function of (seed, i) and the mesh alone: bitwise reproducible, and a prefix of a longer
+    run.  A face with a repeated index, of zero area, or more than 2^32 times smaller than the largest face is never
+    chosen.  ValueError before the sampling launch on a bad argument and when no face has area (n > 0).  Host reads:
+    finiteness, the index range, the CDF's total."""
+    V = _finite_vertices(vertices)
+    _, F = _faces_arg(faces, V)
+    n, seed = _count_arg(n), _seed_arg(seed)
+    if normals not in (None, "face", "vertex"):
+        raise ValueError(f"normals must be None, 'face' or 'vertex', got {normals!r}")
+    if (normals == "vertex") != (vertex_normals is not None):
+        raise ValueError("vertex_normals goes with normals='vertex', and only with it")
+    if vertex_normals is not None:
+        need(vertex_normals, "vertex_normals")
+        if tuple(vertex_normals.shape) != (V, 3):
+            raise ValueError(f"vertex_normals must be ({V},3), got {tuple(vertex_normals.shape)}")
+        if V and not bool(torch.isfinite(vertex_normals).all()):
+            raise ValueError("vertex_normals must be finite")
+    dev = vertices.device
+    points = torch.empty((n, 3), dtype=F32, device=dev)
+    face_idx = torch.empty(n, dtype=torch.int32, device=dev)
+    nrm = torch.empty((n, 3), dtype=F32, device=dev) if normals else None
+    if n:
+        cdf, total = mesh_area_cdf(mesh_face_areas(vertices, faces, ranges_checked=True))
+        if total <= 0:
+            raise ValueError("no face of the mesh has area: nothing to sample")
+        check(lib().nerf_mesh_sample_surface(ptr(vertices), ptr(faces), F, ptr(cdf), total, ptr(vertex_normals), n,
+                                             seed, ptr(points), ptr(face_idx), ptr(nrm), stream()),
+              "nerf_mesh_sample_surface")
+    return (points, face_idx, nrm) if normals else (points, face_idx)
+
+
+MAX_GRID_DIM = 1024
+
+
+def _points_arg(points, name):
+    need(points, name)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{name} must be (N,3), got {tuple(points.shape)}")
+    if points.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name} must have fewer than 2^31 rows")
+    return int(points.shape[0])
+
+
+def _gather3(src, idx):
+    n = int(idx.shape[0])
+    dst = torch.empty((n, 3), dtype=F32, device=src.device)
+    if n:
+        check(lib().nerf_gather_rows(ptr(src), 3, ptr(idx), n, 3, ptr(dst), 3, stream()), "nerf_gather_rows")
+    return dst
+
+
+def _sorted_cell_keys(points, m, lo_c, inv, dims_c):
+    """(sorted keys (m,) int64, the original index of every sorted position (m,) int32)"""
+    keys = torch.empty(m, dtype=torch.int64, device=points.device)
+    check(lib().nerf_points_cell_keys(ptr(points), m, lo_c, inv, dims_c, ptr(keys), stream()), "nerf_points_cell_keys")
+    keys = torch.sort(keys).values
+    return keys, (keys & 0xffffffff).to(torch.int32)
+
+
+def points_grid(points, cell_size=None):
+    """The search grid of a reference point set (nerf_points_cell_keys -> torch.sort -> nerf_gather_rows): points
+    (m,3) float32, finite.  Returns the dict {keys (m,) int64 sorted, points (m,3) float32 in key order, lo (3 floats),
+    cell, inv (fp32 values as floats), dims (3 ints), m}.  lo is the minimum of the points.  The default cell is
+    longest extent / clamp(ceil(sqrt(m) / 2), 1, 1024), a handful of surface samples per occupied cell; an all-zero
+    extent gets cell = 1.  dims = floor((max - lo) * inv) + 1 per axis in fp32 (1 for an axis of zero extent).
+    ``cell_size``: a finite positive float; ValueError if it needs more than 1024 cells on an axis (the cap keeps the
+    fp32 cell index within 2^-12 of a cell, which the search's stopping rule rests on).  Memory: 8 + 12 bytes per
+    point beyond the input, no cell table.  One host read: the box (it carries the finiteness check)."""
+    import math
+
+    import numpy as np
+    m = _points_arg(points, "points")
+    if cell_size is not None:
+        with np.errstate(all="ignore"):
+            try:
+                cell = np.float32(cell_size)
+            except (TypeError, ValueError):
+                raise ValueError(f"cell_size must be a float, got {cell_size!r}") from None
+            inv = np.float32(1.0) / cell
+        if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
+            raise ValueError(f"cell_size must be a finite positive float32 with a finite reciprocal, got {cell_size!r}")
+    dev = points.device
+    if m == 0:
+        cell = np.float32(1.0) if cell_size is None else cell
+        return {"keys": torch.empty(0, dtype=torch.int64, device=dev), "points": points.new_empty((0, 3)),
+                "lo": [0.0, 0.0, 0.0], "cell": float(cell), "inv": float(np.float32(1.0) / cell), "dims": [1, 1, 1],
+                "m": 0}
+    mm = [torch.aminmax(points[:, c]) for c in range(3)]
+    box = np.asarray(torch.stack([x.min for x in mm] + [x.max for x in mm]).tolist(), np.float32)
+    if not np.isfinite(box).all():
+        raise ValueError("points must be finite")
+    lo = box[:3]
+    with np.errstate(all="ignore"):
+        ext = box[3:] - lo
+        if not np.isfinite(ext).all():
+            raise ValueError("the extent of the points overflows float32")
+        if cell_size is None:
+            k = min(max(math.ceil(math.sqrt(m) / 2.0), 1), MAX_GRID_DIM)
+            cell = ext.max() / np.float32(k) if ext.max() > 0 else np.float32(1.0)
+            inv = np.float32(1.0) / cell
+            if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
+                cell, inv = np.float32(1.0), np.float32(1.0)  # an extent too small to divide: one cell holds it all
+        cells = np.floor(ext * inv)  # fp32, like the kernel's cell index of the largest coordinate
+    if cell_size is None:
+        cells = np.minimum(cells, MAX_GRID_DIM - 1)  # only rounding can exceed it; the kernel clamps into the last cell
+    elif not np.isfinite(cells).all() or cells.max() + 1 > MAX_GRID_DIM:
+        raise ValueError(f"cell_size {cell_size!r} needs more than {MAX_GRID_DIM} cells along an axis")
+    dims = [int(c) + 1 for c in cells]
+    lo_c, dims_c = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int32 * 3)(*dims)
+    keys, order = _sorted_cell_keys(points, m, lo_c, float(inv), dims_c)
+    return {"keys": keys, "points": _gather3(points, order), "lo": lo.tolist(), "cell": float(cell),
+            "inv": float(inv), "dims": dims, "m": m}
+
+
+def _finite_points(points, name):
+    n = _points_arg(points, name)
+    if n and not bool(torch.isfinite(points).all()):
+        raise ValueError(f"{name} must be finite")
+    return n
+
+
+def points_nearest(query, grid, sort_queries=True, finite_checked=False):
+    """The nearest reference point of every query (nerf_points_nearest): query (n,3) float32, finite; ``grid`` of
+    points_grid.  Returns (d2 (n,) float32, idx (n,) int32): d2 = (dx dx + dy dy) + dz dz in fp32 to the nearest point,
+    idx its row in the reference set, the smallest row on equal d2; exactly what a brute-force search gives, bit for
+    bit.  An empty reference set gives d2 = +inf, idx = -1.  ``sort_queries``: present the queries in the order of
+    their own cell keys (one more key launch, sort and gather, the results scattered back) so that the lanes of a
+    wave walk the same columns; the result is the same either way.  One host read: the finiteness of the queries
+    (skipped with ``finite_checked``)."""
+    n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
+    if not isinstance(grid, dict) or not {"keys", "points", "lo", "cell", "inv", "dims", "m"} <= set(grid):
+        raise ValueError("grid must be the dict that points_grid returns")
+    m = int(grid["m"])
+    dev = query.device
+    d2 = torch.empty(n, dtype=F32, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return d2, idx
+    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
+    cell, inv = float(grid["cell"]), float(grid["inv"])
+    L = lib()
+
+    def run(q, out_d2, out_idx):
+        check(L.nerf_points_nearest(ptr(q), n, ptr(grid["keys"]) if m else None, ptr(grid["points"]) if m else None,
+                                    m, lo_c, cell, inv, dims_c, ptr(out_d2), ptr(out_idx), stream()),
+              "nerf_points_nearest")
+
+    if not sort_queries or m == 0:
+        run(query, d2, idx)
+        return d2, idx
+    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
+    sd2, sidx = torch.empty_like(d2), torch.empty_like(idx)
+    run(_gather3(query, order), sd2, sidx)
+    order = order.to(torch.int64)
+    d2[order] = sd2
+    idx[order] = sidx
+    return d2, idx
+
+
 # ------------------------------------------------------------------ optimiser
 
 

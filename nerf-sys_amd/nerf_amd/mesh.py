@@ -17,6 +17,10 @@ and removes the zero-area triangles.
 Smoothing on the device (csrc/mesh_smooth.hip): Mesh.smooth runs Taubin (or plain Laplacian) passes
 over a CSR vertex adjacency built once, with open boundaries held fixed by default; Mesh.compute_normals derives
 area-weighted vertex normals from the faces.
+
+Metrics on the device (csrc/mesh_metrics.hip, nerf_amd/mesh_metrics.py): Mesh.face_areas / area,
+Mesh.sample_surface draws points uniformly by area, Mesh.distance_to reports Chamfer, Hausdorff, F-score and normal
+consistency against another mesh.
 """
 from __future__ import annotations
 
@@ -277,6 +281,39 @@ class Mesh:
                 i ^= 1
         normals = None if self.normals is None else self._face_normals(cur, ranges_checked=True)
         return Mesh(cur, f, normals, self.colors)
+
+    # ---- metrics on the device (kernels.mesh_face_areas / mesh_sample_surface, mesh_metrics)
+
+    def face_areas(self) -> torch.Tensor:
+        """(F,) float64: the area of every face, computed in double; exactly 0 for a face with a repeated index.
+        ValueError on non-finite vertices and out-of-range indices."""
+        return K.mesh_face_areas(self.vertices, self.faces)
+
+    def area(self) -> float:
+        """The surface area: the float64 torch sum of face_areas()."""
+        return float(self.face_areas().sum())
+
+    def sample_surface(self, n, seed=0, normals=None):
+        """``n`` points distributed uniformly by area over the faces: (points (n,3) float32, face_idx (n,) int32), and
+        with ``normals`` = "face" (the sampled face's unit normal, by its winding) or "vertex" (the barycentric mix of
+        the mesh's vertex normals, normalised; the mesh must have normals) also (n,3) float32 unit normals.  Sample i
+        depends on (seed, i) and the mesh alone: bitwise reproducible.  Faces of zero area, and faces more than 2^32
+        times smaller than the largest, are never chosen.  ValueError before the sampling launch on ``n`` that is no
+        int >= 0, a bad ``seed`` or ``normals``, non-finite vertices, out-of-range indices, and a mesh without area."""
+        if normals == "vertex" and self.normals is None:
+            raise ValueError("normals='vertex' needs a mesh with vertex normals (Mesh.compute_normals)")
+        return K.mesh_sample_surface(self.vertices, self.faces, n, seed=seed, normals=normals,
+                                     vertex_normals=self.normals if normals == "vertex" else None)
+
+    def distance_to(self, other, n_samples=2 ** 18, seed=0, thresholds=(), normals=False) -> dict:
+        """mesh_metrics.mesh_distance(self, other, ...): Chamfer, Hausdorff, precision / recall / F-score at
+        ``thresholds`` and (``normals``) normal consistency between ``n_samples`` area-uniform samples of each mesh,
+        as a dict of floats with self as a and other as b.  The point-set distance: it overestimates the distance
+        between the surfaces by up to the sampling spacing, about sqrt(area / n_samples)."""
+        from .mesh_metrics import mesh_distance
+        if not isinstance(other, Mesh):
+            raise ValueError(f"other must be a Mesh, got {type(other).__name__}")
+        return mesh_distance(self, other, n_samples=n_samples, seed=seed, thresholds=thresholds, normals=normals)
 
 
 def _box(lo, hi):

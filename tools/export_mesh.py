@@ -26,6 +26,12 @@ The JSON line then also reports the faces before the clustering.
 before normals and colours are evaluated; "grid" normals become the face-derived normals of the smoothed surface.
 
   python tools/export_mesh.py --train-steps 2000 --min-faces 200 --smooth 10 --out mesh.ply
+
+--report-error (off by default; the files and the first JSON line are unchanged) prints a second JSON line with
+Mesh.distance_to between the surface before --simplify / --smooth (after the component filter) and the
+exported one: Chamfer, Hausdorff and F-score at one and two lattice spacings, from --error-samples points per surface.
+
+  python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --smooth 10 --report-error --out mesh.ply
 """
 import argparse
 import json
@@ -66,6 +72,9 @@ def main():
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
                     help="vertex clustering with cells of this edge (world units)")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="Taubin smoothing iterations")
+    ap.add_argument("--report-error", action="store_true",
+                    help="also print the distance between the surface before --simplify / --smooth and the exported one")
+    ap.add_argument("--error-samples", type=int, default=2 ** 18, help="points per surface for --report-error")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -121,6 +130,17 @@ def main():
                       "smooth": a.smooth,
                       "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
                       "extract_seconds": round(dt, 4), "out": a.out}))
+    if a.report_error:
+        # the surface the clustering and the smoothing started from: extracted again, filtered, nothing else
+        before = model.extract_mesh(resolution=a.resolution, threshold=a.threshold, normals=None,
+                                    min_faces=a.min_faces, keep_largest=a.keep_largest)
+        h = (AABB[1][0] - AABB[0][0]) / (a.resolution - 1)
+        if mesh.faces.shape[0] == 0 or before.faces.shape[0] == 0:
+            print(json.dumps({"report_error": None, "reason": "a surface without faces has no samples"}))
+        else:
+            err = mesh.distance_to(before, n_samples=a.error_samples, thresholds=(h, 2 * h))
+            print(json.dumps({"report_error": {"a": "exported", "b": "before simplify / smooth",
+                                               "samples": a.error_samples, "lattice_spacing": h, **err}}))
 
 
 if __name__ == "__main__":
