@@ -793,6 +793,40 @@ int nerf_points_nearest(const float* query, int64_t n, const int64_t* sorted_key
                         int64_t m, const float* lo, float cell, float inv, const int32_t* dims, float* d2,
                         int32_t* idx, hipStream_t stream);
 
+/* Exact point-to-surface distance: the nearest FACE of every query, its squared distance and the
+ * closest point on it, through the uniform grid of the mesh metrics with faces binned by bounding box.  vertices
+ * (V,3) float32 finite, faces (F,3) int32 with 0 <= index < V, query (n,3) float32 finite: the kernels check neither,
+ * the caller does.  3 F, n and n_keys below 2^31, every dim in [1, 1024], cell and inv finite and positive, else
+ * NERF_E_ARG; the int64 and double arrays 8-byte aligned, else NERF_E_ALIGN; both before any launch.  lo (3 floats)
+ * and dims (3 int32) are HOST arrays and the grid's box [lo, lo + dims cell] must hold every vertex (up to rounding).
+ * No LDS, no atomics, one writer per output: equal inputs give equal bits.  Every fp64 operation rounds on its own.
+ * nerf_mesh_face_cell_counts: counts[f] (F) int64 = the number of cells of the index box
+ *   [cell_index(min corner), cell_index(max corner)] of face f on the three axes (fminf / fmaxf over its corners, the
+ *   fp32 cell index of nerf_points_cell_keys), at most 2^30.  One thread per face.
+ * nerf_mesh_face_cell_keys: offsets (F) int64 = the CALLER's exclusive sum of the counts; face f writes its
+ *   counts[f] keys (cell_id << 32) | f at keys[offsets[f] ..] in ascending cell_id order.  The CALLER sorts all keys
+ *   ascending (any int64 sort) and keeps their number below 2^31.  One thread per face.
+ * nerf_mesh_nearest_faces: for every query the nearest of the faces behind sorted_keys (n_keys): d2[i] (double) = the
+ *   squared distance to the closest point of that face, face[i] = its index, the smallest on equal d2, closest (n,3)
+ *   float32 or NULL = that point rounded to fp32: a brute-force search's result bit for bit.  The closest point is
+ *   computed in double from the fp32 corners by the region walk of Ericson, Real-Time Collision Detection §5.1.5 (vertex
+ *   a, vertex b, edge ab, vertex c, edge ac, edge bc, interior), dot products (x x' + y y') + z z', every edge
+ *   parameter and interior weight clamped to [0, 1]; a face with a repeated index, with a cross product of exactly
+ *   (0, 0, 0) or with va + vb + vc <= 0 in the interior is measured as its three edges ab, ac, bc (the earlier edge
+ *   on a tie): no NaN, no division by zero.  d2 = (dx dx + dy dy) + dz dz of d = query - point in double.  The search
+ *   walks the shells, columns and runs of nerf_points_nearest, measures every face key of a run (a face registered in
+ *   several cells more than once) and stops before shell r >= 2 once best_d2, rounded up to fp32, satisfies the rule
+ *   of nerf_points_nearest (the argument: mesh_distance_core.hpp).  n_keys = 0: d2 = +inf, face = -1, closest = the
+ *   query.  One thread per query. */
+int nerf_mesh_face_cell_counts(const float* vertices, const int32_t* faces, int64_t F, const float* lo, float inv,
+                               const int32_t* dims, int64_t* counts, hipStream_t stream);
+int nerf_mesh_face_cell_keys(const float* vertices, const int32_t* faces, int64_t F, const float* lo, float inv,
+                             const int32_t* dims, const int64_t* offsets, int64_t* keys, hipStream_t stream);
+int nerf_mesh_nearest_faces(const float* query, int64_t n, const int64_t* sorted_keys, int64_t n_keys,
+                            const float* vertices, const int32_t* faces, int64_t F, const float* lo, float cell,
+                            float inv, const int32_t* dims, double* d2, int32_t* face, float* closest,
+                            hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -169,6 +169,9 @@ def lib():
             "nerf_mesh_sample_surface": [P, P, I64, P, U64, P, I64, U64, P, P, P, P],
             "nerf_points_cell_keys": [P, I64, P, F, P, P, P],
             "nerf_points_nearest": [P, I64, P, P, I64, P, F, F, P, P, P, P],
+            "nerf_mesh_face_cell_counts": [P, P, I64, P, F, P, P, P],
+            "nerf_mesh_face_cell_keys": [P, P, I64, P, F, P, P, P, P],
+            "nerf_mesh_nearest_faces": [P, I64, P, I64, P, P, I64, P, F, F, P, P, P, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -233,7 +236,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_cluster_faces_workspace_bytes", "nerf_mesh_cluster_faces",
            "nerf_mesh_pair_keys", "nerf_mesh_csr_flags", "nerf_mesh_csr_build", "nerf_mesh_smooth_pass",
            "nerf_mesh_vertex_normals",
-           "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest")
+           "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",
+           "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces")
 
 
 def check(status: int, what: str) -> None:

@@ -932,6 +932,143 @@ def points_nearest(query, grid, sort_queries=True, finite_checked=False):
     return d2, idx
 
 
+# ------------------------------------------------------------------ exact point-to-surface distance
+
+
+def _cell_size_arg(cell_size):
+    """(cell, inv) as fp32 numpy values: ValueError unless cell_size is a finite positive float32 with a finite
+    reciprocal (the rule of points_grid)."""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        try:
+            cell = np.float32(cell_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"cell_size must be a float, got {cell_size!r}") from None
+        inv = np.float32(1.0) / cell
+    if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
+        raise ValueError(f"cell_size must be a finite positive float32 with a finite reciprocal, got {cell_size!r}")
+    return cell, inv
+
+
+_FACE_GRID_KEYS = {"keys", "lo", "cell", "inv", "dims", "n_keys", "F"}
+
+
+def mesh_face_grid(vertices, faces, cell_size=None):
+    """The search grid of a mesh's faces (nerf_mesh_face_cell_counts -> torch.cumsum -> nerf_mesh_face_cell_keys ->
+    torch.sort): vertices (V,3) float32, finite; faces (F,3) int32.  Returns the dict {keys (n_keys,) int64 sorted, lo
+    (3 floats), cell, inv (fp32 values as floats), dims (3 ints), n_keys, F}.  A face is registered in every cell of
+    the index box of its bounding box, key = (cell_id << 32) | face; binning is by bounding box, not by exact
+    triangle / box overlap.  lo and the box are those of ALL vertices, used by a face or not (a vertex no face uses
+    only enlarges the grid).  The default cell is longest extent / clamp(ceil(sqrt(F) / 2), 1, 1024), about two faces
+    of an even triangulation per cell edge; an all-zero extent gets cell = 1.  dims = floor((max - lo) * inv) + 1 per
+    axis in fp32.  ``cell_size``: a finite positive float; ValueError if it needs more than 1024 cells on an axis, and
+    ValueError before the key launch when the faces have 2^31 keys or more between them (a finer cell_size, or faces
+    that span the grid, multiply the keys: 8 bytes each).  F == 0 gives an empty grid.  Host reads: the box (it carries
+    the finiteness check), the index range, the total number of keys."""
+    import math
+
+    import numpy as np
+    V = _vertices_arg(vertices)
+    _, F = _faces_arg(faces, V)
+    if cell_size is not None:
+        cell, inv = _cell_size_arg(cell_size)
+    dev = vertices.device
+    if V:
+        mm = [torch.aminmax(vertices[:, c]) for c in range(3)]
+        box = np.asarray(torch.stack([x.min for x in mm] + [x.max for x in mm]).tolist(), np.float32)
+        if not np.isfinite(box).all():
+            raise ValueError("vertices must be finite")
+    if F == 0:
+        cell = np.float32(1.0) if cell_size is None else cell
+        return {"keys": torch.empty(0, dtype=torch.int64, device=dev), "lo": [0.0, 0.0, 0.0], "cell": float(cell),
+                "inv": float(np.float32(1.0) / cell), "dims": [1, 1, 1], "n_keys": 0, "F": 0}
+    lo = box[:3]
+    with np.errstate(all="ignore"):
+        ext = box[3:] - lo
+        if not np.isfinite(ext).all():
+            raise ValueError("the extent of the vertices overflows float32")
+        if cell_size is None:
+            k = min(max(math.ceil(math.sqrt(F) / 2.0), 1), MAX_GRID_DIM)
+            cell = ext.max() / np.float32(k) if ext.max() > 0 else np.float32(1.0)
+            inv = np.float32(1.0) / cell
+            if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
+                cell, inv = np.float32(1.0), np.float32(1.0)  # an extent too small to divide: one cell holds it all
+        cells = np.floor(ext * inv)  # fp32, like the kernel's cell index of the largest coordinate
+    if cell_size is None:
+        cells = np.minimum(cells, MAX_GRID_DIM - 1)  # only rounding can exceed it; the kernel clamps into the last cell
+    elif not np.isfinite(cells).all() or cells.max() + 1 > MAX_GRID_DIM:
+        raise ValueError(f"cell_size {cell_size!r} needs more than {MAX_GRID_DIM} cells along an axis")
+    dims = [int(c) + 1 for c in cells]
+    lo_c, dims_c = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int32 * 3)(*dims)
+    L = lib()
+    counts = torch.empty(F, dtype=torch.int64, device=dev)
+    check(L.nerf_mesh_face_cell_counts(ptr(vertices), ptr(faces), F, lo_c, float(inv), dims_c, ptr(counts), stream()),
+          "nerf_mesh_face_cell_counts")
+    ends = torch.cumsum(counts, 0)
+    n_keys = int(ends[-1])
+    if n_keys >= 2 ** 31:
+        raise ValueError(f"the faces are registered in {n_keys} cells, 2^31 or more: use a larger cell_size")
+    keys = torch.empty(n_keys, dtype=torch.int64, device=dev)
+    check(L.nerf_mesh_face_cell_keys(ptr(vertices), ptr(faces), F, lo_c, float(inv), dims_c, ptr(ends - counts),
+                                     ptr(keys), stream()), "nerf_mesh_face_cell_keys")
+    return {"keys": torch.sort(keys).values, "lo": lo.tolist(), "cell": float(cell), "inv": float(inv), "dims": dims,
+            "n_keys": n_keys, "F": F}
+
+
+def mesh_nearest_faces(query, vertices, faces, grid, sort_queries=True, closest=True, finite_checked=False):
+    """The nearest face of every query (nerf_mesh_nearest_faces): query (n,3) float32, finite; vertices and faces the
+    mesh that ``grid`` = mesh_face_grid(vertices, faces) was built from.  Returns (d2 (n,) float64, face (n,) int32)
+    and, with ``closest``, the closest point (n,3) float32: d2 is the squared distance, in double, from the query to
+    the closest point of the face (Ericson's region walk over the fp32 corners), face the nearest
+    face, the smallest index on equal d2, and the point that closest point rounded to fp32; exactly what a brute-force
+    search over all faces gives, bit for bit.  A face without area counts as its three edges.  A mesh without faces
+    gives d2 = +inf, face = -1 and the query itself as the point.  ``sort_queries``: present the queries in the order
+    of their own cell keys (as points_nearest does); the result is the same either way.  Host reads: the finiteness of
+    the queries and of the vertices and the index range, all three skipped with ``finite_checked`` (the caller has
+    made them, as mesh_face_grid does for the mesh)."""
+    n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
+    V = _vertices_arg(vertices) if finite_checked else _finite_vertices(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
+    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
+        raise ValueError("grid must be the dict that mesh_face_grid returns")
+    n_keys = int(grid["n_keys"])
+    keys = grid["keys"]
+    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
+            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
+        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
+    if n_keys:
+        need(keys, "grid['keys']", torch.int64)
+    dev = query.device
+    d2 = torch.empty(n, dtype=torch.float64, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    point = torch.empty((n, 3), dtype=F32, device=dev) if closest else None
+    if n == 0:
+        return (d2, face, point) if closest else (d2, face)
+    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
+    cell, inv = float(grid["cell"]), float(grid["inv"])
+    L = lib()
+
+    def run(q, out_d2, out_face, out_point):
+        check(L.nerf_mesh_nearest_faces(ptr(q), n, ptr(keys) if n_keys else None, n_keys,
+                                        ptr(vertices) if n_keys else None, ptr(faces) if n_keys else None, F, lo_c,
+                                        cell, inv, dims_c, ptr(out_d2), ptr(out_face), ptr(out_point), stream()),
+              "nerf_mesh_nearest_faces")
+
+    if not sort_queries or n_keys == 0:
+        run(query, d2, face, point)
+        return (d2, face, point) if closest else (d2, face)
+    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
+    sd2, sface = torch.empty_like(d2), torch.empty_like(face)
+    spoint = torch.empty_like(point) if closest else None
+    run(_gather3(query, order), sd2, sface, spoint)
+    order = order.to(torch.int64)
+    d2[order] = sd2
+    face[order] = sface
+    if closest:
+        point[order] = spoint
+    return (d2, face, point) if closest else (d2, face)
+
+
 # ------------------------------------------------------------------ optimiser
 
 

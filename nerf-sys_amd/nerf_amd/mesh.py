@@ -20,7 +20,8 @@ area-weighted vertex normals from the faces.
 
 Metrics on the device (csrc/mesh_metrics.hip, nerf_amd/mesh_metrics.py): Mesh.face_areas / area,
 Mesh.sample_surface draws points uniformly by area, Mesh.distance_to reports Chamfer, Hausdorff, F-score and normal
-consistency against another mesh.
+consistency against another mesh.  Mesh.closest_points and distance_to(exact=True) measure against the triangles
+themselves (csrc/mesh_distance.hip).
 """
 from __future__ import annotations
 
@@ -305,15 +306,25 @@ class Mesh:
         return K.mesh_sample_surface(self.vertices, self.faces, n, seed=seed, normals=normals,
                                      vertex_normals=self.normals if normals == "vertex" else None)
 
-    def distance_to(self, other, n_samples=2 ** 18, seed=0, thresholds=(), normals=False) -> dict:
+    def distance_to(self, other, n_samples=2 ** 18, seed=0, thresholds=(), normals=False, exact=False) -> dict:
         """mesh_metrics.mesh_distance(self, other, ...): Chamfer, Hausdorff, precision / recall / F-score at
         ``thresholds`` and (``normals``) normal consistency between ``n_samples`` area-uniform samples of each mesh,
         as a dict of floats with self as a and other as b.  The point-set distance: it overestimates the distance
-        between the surfaces by up to the sampling spacing, about sqrt(area / n_samples)."""
+        between the surfaces by up to the sampling spacing, about sqrt(area / n_samples).  ``exact``: measure every
+        sample against the other mesh's triangles instead of its samples: no sampling floor."""
         from .mesh_metrics import mesh_distance
         if not isinstance(other, Mesh):
             raise ValueError(f"other must be a Mesh, got {type(other).__name__}")
-        return mesh_distance(self, other, n_samples=n_samples, seed=seed, thresholds=thresholds, normals=normals)
+        return mesh_distance(self, other, n_samples=n_samples, seed=seed, thresholds=thresholds, normals=normals,
+                             exact=exact)
+
+    def closest_points(self, query, cell_size=None):
+        """mesh_metrics.nearest_on_mesh(query, self, cell_size): for every row of ``query`` (n,3) float32 the squared
+        distance in double to the nearest triangle, that face's index (the smallest on equal distance) and the closest
+        point on it: (d2 (n,) float64, face (n,) int32, closest (n,3) float32), a brute-force search's result bit for
+        bit."""
+        from .mesh_metrics import nearest_on_mesh
+        return nearest_on_mesh(query, self, cell_size)
 
 
 def _box(lo, hi):

@@ -8,8 +8,12 @@ few float64 torch ops, so equal inputs give equal dicts.
 
 This is the POINT-SET distance.  The distance from a sample to the nearest SAMPLE of the other surface overestimates
 its distance to that surface by up to the sampling spacing (about sqrt(area / n_samples)), so two identical meshes
-sampled with different seeds give a small non-zero Chamfer; with the same seed they give exactly 0.  Exact
-point-to-triangle distance is out of scope.
+sampled with different seeds give a small non-zero Chamfer; with the same seed they give exactly 0.
+
+The EXACT path (csrc/mesh_distance.hip) removes that floor: nearest_on_mesh returns, for every query,
+the squared distance in double to the nearest TRIANGLE, that face and the closest point on it, through a uniform grid
+of the faces (kernels.mesh_face_grid / mesh_nearest_faces), and mesh_distance(..., exact=True) measures the samples of
+each mesh against the surface of the other.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["nearest_points", "point_set_metrics", "mesh_distance"]
+__all__ = ["nearest_points", "nearest_on_mesh", "point_set_metrics", "mesh_distance"]
 
 DEFAULT_SAMPLES = 2 ** 18
 
@@ -86,6 +90,17 @@ def point_set_metrics(a, b, thresholds=(), normals_a=None, normals_b=None, cell_
     grid_a = K.points_grid(a, cell_size)
     d2_ab, idx_ab = K.points_nearest(a, grid_b, finite_checked=True)
     d2_ba, idx_ba = K.points_nearest(b, grid_a, finite_checked=True)
+    cosines = None
+    if normals_a is not None:
+        na, nb = normals_a.to(torch.float64), normals_b.to(torch.float64)
+        cosines = (na * nb[idx_ab.to(torch.int64)]).sum(1), (nb * na[idx_ba.to(torch.int64)]).sum(1)
+    return _report(d2_ab, d2_ba, taus, cosines)
+
+
+def _report(d2_ab, d2_ba, taus, cosines=None):
+    """The dict of point_set_metrics from the two arrays of squared distances (fp32 or float64) and, for
+    normal_consistency, the two arrays of cosines between every item's normal and its nearest neighbour's."""
+    n, m = d2_ab.shape[0], d2_ba.shape[0]
     ab, ba = _side(d2_ab), _side(d2_ba)
     names = ["a_to_b_mean", "a_to_b_rms", "a_to_b_max", "b_to_a_mean", "b_to_a_rms", "b_to_a_max", "chamfer",
              "chamfer_sq", "hausdorff"]
@@ -96,27 +111,74 @@ def point_set_metrics(a, b, thresholds=(), normals_a=None, normals_b=None, cell_
         f = torch.where(p + r > 0, 2 * p * r / torch.clamp(p + r, min=1e-300), torch.zeros_like(p))
         names += [f"precision@{tau}", f"recall@{tau}", f"fscore@{tau}"]
         vals += [p, r, f]
-    if normals_a is not None:
-        na, nb = normals_a.to(torch.float64), normals_b.to(torch.float64)
-        c_ab = (na * nb[idx_ab.to(torch.int64)]).sum(1).abs().mean()
-        c_ba = (nb * na[idx_ba.to(torch.int64)]).sum(1).abs().mean()
+    if cosines is not None:
+        c_ab = cosines[0].abs().mean()
+        c_ba = cosines[1].abs().mean()
         names.append("normal_consistency")
         vals.append((c_ab + c_ba) / 2)
     return dict(zip(names, torch.stack(vals).tolist()))  # one host read
 
 
-def mesh_distance(mesh_a, mesh_b, n_samples=DEFAULT_SAMPLES, seed=0, thresholds=(), normals=False, cell_size=None):
+def nearest_on_mesh(query, mesh, cell_size=None):
+    """(d2 (n,) float64, face (n,) int32, closest (n,3) float32): for every row of ``query`` (n,3) the squared
+    distance, in double, to the nearest triangle of ``mesh`` (a Mesh on the device), that face's index, the smallest
+    on equal distance, and the closest point on it rounded to fp32: a brute-force search's result over all faces,
+    bit for bit (kernels.mesh_nearest_faces).  A face without area counts as its three edges.  A mesh
+    without faces gives +inf, -1 and the query itself.  ``cell_size``: the edge of the search grid's cells (default:
+    kernels.mesh_face_grid's rule).  ValueError before any launch on CPU tensors, wrong dtypes or shapes, non-finite
+    queries or vertices, out-of-range indices, a cell_size that is not finite and positive or that needs more than
+    1024 cells along an axis, and before the key launch on a grid of 2^31 keys or more."""
+    K._finite_points(query, "query")
+    grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)
+    return K.mesh_nearest_faces(query, mesh.vertices, mesh.faces, grid, finite_checked=True)
+
+
+def _unit_face_normals(mesh):
+    """(F,3) float64: nerf_mm::face_cross of every face in float64 torch ops, divided by its length; zeros for a zero
+    cross product."""
+    p = mesh.vertices.to(torch.float64)
+    f = mesh.faces.to(torch.int64)
+    o = p[f[:, 0]]
+    a, b = p[f[:, 1]] - o, p[f[:, 2]] - o
+    c = torch.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+    d = torch.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2])
+    return c / torch.where(d > 0, d, torch.ones_like(d))[:, None]
+
+
+def mesh_distance(mesh_a, mesh_b, n_samples=DEFAULT_SAMPLES, seed=0, thresholds=(), normals=False, cell_size=None,
+                  exact=False):
     """point_set_metrics between ``n_samples`` area-uniform samples of each of two meshes (Mesh.sample_surface with the
     same ``seed`` on both, so a mesh against itself gives exactly 0).  ``normals``: add normal_consistency from the
     faces' own normals.  The point-set distance: sample-to-sample distance overestimates sample-to-surface distance by
     up to the sampling spacing, about sqrt(area / n_samples).  ValueError before any launch on bad arguments, on
-    n_samples < 1, and on a mesh without a face of positive area."""
+    n_samples < 1, and on a mesh without a face of positive area.
+
+    ``exact``: measure the samples of a against the SURFACE of b and the samples of b against the surface of a
+    (nearest_on_mesh, float64 squared distances); the same keys with the same definitions, normal_consistency from the
+    sample's face normal against the unit normal of the nearest face (0 for a face whose cross product is zero), and
+    ``cell_size`` the cell of the two face grids.  No sampling floor: a mesh against itself gives distances of the
+    order of the fp32 rounding of the samples, whatever the seeds."""
     K._count_arg(n_samples, "n_samples")
     if n_samples < 1:
         raise ValueError(f"n_samples must be >= 1, got {n_samples!r}")
-    _thresholds(thresholds)
+    taus = _thresholds(thresholds)
     kind = "face" if normals else None
     sa = mesh_a.sample_surface(n_samples, seed=seed, normals=kind)
     sb = mesh_b.sample_surface(n_samples, seed=seed, normals=kind)
-    return point_set_metrics(sa[0], sb[0], thresholds, sa[2] if normals else None, sb[2] if normals else None,
-                             cell_size=cell_size)
+    if not exact:
+        return point_set_metrics(sa[0], sb[0], thresholds, sa[2] if normals else None, sb[2] if normals else None,
+                                 cell_size=cell_size)
+    # the samples are finite (finite vertices) and sample_surface has checked both meshes
+    grid_b = K.mesh_face_grid(mesh_b.vertices, mesh_b.faces, cell_size)
+    grid_a = K.mesh_face_grid(mesh_a.vertices, mesh_a.faces, cell_size)
+    d2_ab, face_ab = K.mesh_nearest_faces(sa[0], mesh_b.vertices, mesh_b.faces, grid_b, closest=False,
+                                          finite_checked=True)
+    d2_ba, face_ba = K.mesh_nearest_faces(sb[0], mesh_a.vertices, mesh_a.faces, grid_a, closest=False,
+                                          finite_checked=True)
+    cosines = None
+    if normals:
+        na, nb = sa[2].to(torch.float64), sb[2].to(torch.float64)
+        cosines = ((na * _unit_face_normals(mesh_b)[face_ab.to(torch.int64)]).sum(1),
+                   (nb * _unit_face_normals(mesh_a)[face_ba.to(torch.int64)]).sum(1))
+    return _report(d2_ab, d2_ba, taus, cosines)

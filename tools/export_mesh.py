@@ -30,6 +30,8 @@ before normals and colours are evaluated; "grid" normals become the face-derived
 --report-error (off by default; the files and the first JSON line are unchanged) prints a second JSON line with
 Mesh.distance_to between the surface before --simplify / --smooth (after the component filter) and the
 exported one: Chamfer, Hausdorff and F-score at one and two lattice spacings, from --error-samples points per surface.
+With --exact every sample is measured against the other surface's triangles instead of its samples (DESIGN §3.11.5:
+no floor at the sampling spacing) and the line carries "exact": true; without it the line is unchanged.
 
   python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --smooth 10 --report-error --out mesh.ply
 """
@@ -75,6 +77,8 @@ def main():
     ap.add_argument("--report-error", action="store_true",
                     help="also print the distance between the surface before --simplify / --smooth and the exported one")
     ap.add_argument("--error-samples", type=int, default=2 ** 18, help="points per surface for --report-error")
+    ap.add_argument("--exact", action="store_true",
+                    help="--report-error measures the samples against the other surface's triangles, not its samples")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -138,9 +142,10 @@ def main():
         if mesh.faces.shape[0] == 0 or before.faces.shape[0] == 0:
             print(json.dumps({"report_error": None, "reason": "a surface without faces has no samples"}))
         else:
-            err = mesh.distance_to(before, n_samples=a.error_samples, thresholds=(h, 2 * h))
+            err = mesh.distance_to(before, n_samples=a.error_samples, thresholds=(h, 2 * h), exact=a.exact)
             print(json.dumps({"report_error": {"a": "exported", "b": "before simplify / smooth",
-                                               "samples": a.error_samples, "lattice_spacing": h, **err}}))
+                                               "samples": a.error_samples, "lattice_spacing": h,
+                                               **({"exact": True} if a.exact else {}), **err}}))
 
 
 if __name__ == "__main__":
