@@ -827,6 +827,28 @@ int nerf_mesh_nearest_faces(const float* query, int64_t n, const int64_t* sorted
                             float inv, const int32_t* dims, double* d2, int32_t* face, float* closest,
                             hipStream_t stream);
 
+/* Nearest-hit ray casting against a mesh through the face grid above.  rays (n,8) float32 rows
+ * [o, d, near, far] with o and d finite, d not all zero and near / far no NaN, vertices and faces as above: the kernel
+ * checks none of it, the caller does.  The argument checks of nerf_mesh_nearest_faces, and 0 <= margin <= 2^-10 cell
+ * and cull in {0, 1}, else NERF_E_ARG; sorted_keys and t 8-byte aligned, else NERF_E_ALIGN; both before any launch.
+ * nerf_mesh_ray_cast: for every ray the nearest face it hits: t[i] (double) = the ray's own parameter of the hit
+ *   (points are o + t d, d is not normalised), +inf on a miss; face[i] = the face, the smallest index on equal t, -1
+ *   on a miss; bary (n,2) float32 = (u, v) rounded, the hit point being (1 - u - v) a + u b + v c, (0, 0) on a miss: a
+ *   brute-force search's result bit for bit.  Per face, in double from the fp32 values, dot products
+ *   (x x' + y y') + z z', cross products six products and three differences: e1 = b - a, e2 = c - a, p = d x e2,
+ *   det = e1 . p, s = o - a, u = (s . p) / det, q = s x e1, v = (d . q) / det, t = (e2 . q) / det.  Never hit: a face
+ *   with a repeated index, with a cross product of exactly (0, 0, 0), with det == 0 or, with cull, det <= 0 (det > 0:
+ *   the ray runs against the winding normal).  Hit: u >= 0, u <= 1, v >= 0, u + v <= 1, near <= t <= far, and
+ *   o_k + t d_k within [min_k - margin, max_k + margin] of the face's corners on every axis (margin = 2^-30 of the
+ *   largest |coordinate| of the mesh, the caller's); a NaN fails every comparison.  The ray is clipped to the grid's
+ *   box and walks the layers of cells along its major axis, at most 3 x 3 cells per layer, stopping before a layer
+ *   entered after the best t (the argument: mesh_raycast_core.hpp); a ray whose origin lies more than 2^32 cells from
+ *   the grid tests every face.  n_keys = 0: all misses.  One thread per ray. */
+int nerf_mesh_ray_cast(const float* rays, int64_t n, const int64_t* sorted_keys, int64_t n_keys,
+                       const float* vertices, const int32_t* faces, int64_t F, const float* lo, float cell, float inv,
+                       const int32_t* dims, double margin, int cull, double* t, int32_t* face, float* bary,
+                       hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

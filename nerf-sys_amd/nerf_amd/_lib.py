@@ -172,6 +172,7 @@ def lib():
             "nerf_mesh_face_cell_counts": [P, P, I64, P, F, P, P, P],
             "nerf_mesh_face_cell_keys": [P, P, I64, P, F, P, P, P, P],
             "nerf_mesh_nearest_faces": [P, I64, P, I64, P, P, I64, P, F, F, P, P, P, P, P],
+            "nerf_mesh_ray_cast": [P, I64, P, I64, P, P, I64, P, F, F, P, D, I, P, P, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -237,7 +238,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_pair_keys", "nerf_mesh_csr_flags", "nerf_mesh_csr_build", "nerf_mesh_smooth_pass",
            "nerf_mesh_vertex_normals",
            "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",
-           "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces")
+           "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces",
+           "nerf_mesh_ray_cast")
 
 
 def check(status: int, what: str) -> None:

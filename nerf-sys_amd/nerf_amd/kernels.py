@@ -1069,6 +1069,77 @@ def mesh_nearest_faces(query, vertices, faces, grid, sort_queries=True, closest=
     return (d2, face, point) if closest else (d2, face)
 
 
+# ------------------------------------------------------------------ nearest-hit ray casting
+
+
+def _rays_arg(rays, finite_checked=False):
+    """rays (n,8) float32 rows [o, d, near, far]: o and d finite, d not all zero, near and far no NaN (one host read,
+    skipped with ``finite_checked``)."""
+    need(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError(f"rays must be (n,8), got {tuple(rays.shape)}")
+    n = int(rays.shape[0])
+    if n >= 2 ** 31:
+        raise ValueError("rays must have fewer than 2^31 rows")
+    if n and not finite_checked:
+        bad = torch.stack([(~torch.isfinite(rays[:, :6])).any(), (rays[:, 3:6] == 0).all(1).any(),
+                           torch.isnan(rays[:, 6:]).any()]).tolist()
+        if bad[0]:
+            raise ValueError("the origins and directions of the rays must be finite")
+        if bad[1]:
+            raise ValueError("a ray's direction must not be all zeros")
+        if bad[2]:
+            raise ValueError("near and far must not be NaN")
+    return n
+
+
+def mesh_ray_cast(rays, vertices, faces, grid, cull_backfaces=False, finite_checked=False):
+    """The nearest face every ray hits (nerf_mesh_ray_cast): rays (n,8) float32 rows [o, d, near, far] as
+    rays_for_camera packs them, the ray's points o + t d with d not normalised; vertices and faces the mesh that
+    ``grid`` = mesh_face_grid(vertices, faces) was built from.  Returns (t (n,) float64, face (n,) int32, bary (n,2)
+    float32): t the ray's own parameter of the nearest hit with near <= t <= far, +inf on a miss; face the face hit,
+    the smallest index on equal t, -1 on a miss; bary = (u, v), the hit point being (1 - u - v) a + u b + v c of the
+    face's corners, (0, 0) on a miss; exactly what testing every face gives, bit for bit (the test: DESIGN §3.11.6).  A
+    face without area is never hit.  ``cull_backfaces``: only faces whose winding normal points against the ray.
+    ``far < near`` is a miss, +-inf are allowed.  A mesh without faces gives all misses without a launch.
+    ValueError before any launch on CPU tensors, wrong dtypes or shapes, non-finite origins or directions, a direction
+    of all zeros, NaN in near / far, non-finite vertices, out-of-range indices, a grid that is not the face grid of
+    these faces, and a grid whose cell is below 2^-20 of the largest |coordinate| (sixteen fp32 ulps: the walk's
+    argument needs the hit test's box margin within 2^-10 of a cell).  Host reads: the largest |coordinate| (it
+    carries the finiteness of the vertices), and the rays' check and the index range, both skipped with
+    ``finite_checked``."""
+    n = _rays_arg(rays, finite_checked)
+    V = _vertices_arg(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
+    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
+        raise ValueError("grid must be the dict that mesh_face_grid returns")
+    n_keys = int(grid["n_keys"])
+    keys = grid["keys"]
+    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
+            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
+        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
+    if n_keys:
+        need(keys, "grid['keys']", torch.int64)
+    cell, inv = float(grid["cell"]), float(grid["inv"])
+    c_max = float(vertices.abs().max()) if V else 0.0
+    if not c_max < float("inf"):
+        raise ValueError("vertices must be finite")
+    if F and cell < 2.0 ** -20 * c_max:
+        raise ValueError(f"the grid's cell {cell!r} is below 2^-20 of the largest |coordinate| {c_max!r}")
+    dev = rays.device
+    if F == 0 or n == 0:
+        return (torch.full((n,), float("inf"), dtype=torch.float64, device=dev),
+                torch.full((n,), -1, dtype=torch.int32, device=dev), torch.zeros((n, 2), dtype=F32, device=dev))
+    t = torch.empty(n, dtype=torch.float64, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    bary = torch.empty((n, 2), dtype=F32, device=dev)
+    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
+    check(lib().nerf_mesh_ray_cast(ptr(rays), n, ptr(keys), n_keys, ptr(vertices), ptr(faces), F, lo_c, cell, inv,
+                                   dims_c, 2.0 ** -30 * c_max, int(bool(cull_backfaces)), ptr(t), ptr(face), ptr(bary),
+                                   stream()), "nerf_mesh_ray_cast")
+    return t, face, bary
+
+
 # ------------------------------------------------------------------ optimiser
 
 

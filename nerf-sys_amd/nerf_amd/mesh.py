@@ -22,6 +22,10 @@ Metrics on the device (csrc/mesh_metrics.hip, nerf_amd/mesh_metrics.py, DESIGN ย
 Mesh.sample_surface draws points uniformly by area, Mesh.distance_to reports Chamfer, Hausdorff, F-score and normal
 consistency against another mesh.  Mesh.closest_points and distance_to(exact=True) measure against the triangles
 themselves (csrc/mesh_distance.hip, DESIGN ยง3.11.5).
+
+Ray casting on the device (csrc/mesh_raycast.hip, DESIGN ยง3.11.6): Mesh.ray_cast returns the nearest face every ray
+hits, through the same face grid, and Mesh.render the depth, mask, face, normal and colour images of a pinhole view,
+with depth in the ray parameter of ray_rendering.render_image.
 """
 from __future__ import annotations
 
@@ -325,6 +329,64 @@ class Mesh:
         bit (DESIGN ยง3.11.5)."""
         from .mesh_metrics import nearest_on_mesh
         return nearest_on_mesh(query, self, cell_size)
+
+    # ---- ray casting on the device (kernels.mesh_ray_cast, DESIGN ยง3.11.6)
+
+    def ray_cast(self, rays, cell_size=None, cull_backfaces=False, grid=None):
+        """mesh_metrics.ray_cast_mesh(rays, self, ...): for every row [o, d, near, far] of ``rays`` (n,8) float32 the
+        nearest face the ray o + t d hits with near <= t <= far: (t (n,) float64, +inf on a miss; face (n,) int32, -1 on
+        a miss; bary (n,2) float32 = (u, v), the hit point being (1 - u - v) a + u b + v c), the result of testing every
+        face, bit for bit (DESIGN ยง3.11.6).  t is the ray's own parameter: d is not normalised."""
+        from .mesh_metrics import ray_cast_mesh
+        return ray_cast_mesh(rays, self, cell_size=cell_size, cull_backfaces=cull_backfaces, grid=grid)
+
+    def render(self, H, W, fx, fy, cx, cy, c2w, near=0.0, far=float("inf"), cull_backfaces=False, grid=None) -> dict:
+        """The mesh seen from a pinhole camera, through the rays of ray_sampling.rays_for_camera (pixel centres, the
+        camera looking along its -z axis, unit directions): a dict of device tensors,
+          depth  (H,W) float32   the hit's t in the ray parameter of render_image's depth, +inf where nothing is hit
+          mask   (H,W) bool      a face is hit
+          face   (H,W) int32     the face, -1 where nothing is hit
+          normal (H,W,3) float32 with vertex normals their barycentric mix, normalised; without them the unit normal of
+                                 the face by its winding; zeros where nothing is hit
+          color  (H,W,3) float32 only for a mesh with colours: their barycentric mix, zeros where nothing is hit.
+        The cast is Mesh.ray_cast; the gathers and mixes are a few float64 torch ops, rounded to fp32 at the end."""
+        from .ray_sampling import rays_for_camera
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError(f"H and W must be positive, got {H}, {W}")
+        if not isinstance(c2w, torch.Tensor):
+            raise ValueError("c2w must be a (3,4) or (4,4) tensor")
+        K._vertices_arg(self.vertices)
+        dev = self.vertices.device
+        rays = rays_for_camera(H, W, fx, fy, cx, cy, c2w.to(dev), near=float(near), far=float(far))
+        t, face, bary = self.ray_cast(rays, cull_backfaces=cull_backfaces, grid=grid)
+        hit = face >= 0
+        if self.faces.shape[0] == 0:
+            out = {"depth": t.to(torch.float32).view(H, W), "mask": hit.view(H, W), "face": face.view(H, W),
+                   "normal": torch.zeros((H, W, 3), dtype=torch.float32, device=dev)}
+            if self.colors is not None:
+                out["color"] = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+            return out
+        corners = self.faces[face.clamp(min=0).to(torch.int64)].to(torch.int64)  # (n, 3); face 0 stands in at a miss
+        u, v = bary[:, 0].to(torch.float64), bary[:, 1].to(torch.float64)
+        weights = torch.stack([(1.0 - u) - v, u, v], 1)  # (n, 3)
+
+        def mix(attr):
+            return (attr[corners].to(torch.float64) * weights[:, :, None]).sum(1)
+
+        if self.normals is not None:
+            normal = mix(self.normals)
+        else:
+            p = self.vertices[corners].to(torch.float64)  # (n, 3 corners, 3)
+            normal = torch.linalg.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+        normal = normal / torch.linalg.norm(normal, dim=1, keepdim=True).clamp_min(1e-300)
+        out = {"depth": t.to(torch.float32).view(H, W), "mask": hit.view(H, W), "face": face.view(H, W),
+               "normal": (normal * hit[:, None]).to(torch.float32).view(H, W, 3)}
+        if self.colors is not None:
+            c = self.colors[corners]  # (n, 3 corners, 3): the mix stays between the corners' values per channel
+            color = torch.minimum(torch.maximum(mix(self.colors).to(torch.float32), c.amin(1)), c.amax(1))
+            out["color"] = (color * hit[:, None]).view(H, W, 3)
+        return out
 
 
 def _box(lo, hi):

@@ -14,6 +14,9 @@ The EXACT path (csrc/mesh_distance.hip) removes that floor: nea
 the squared distance in double to the nearest TRIANGLE, that face and the closest point on it, through a uniform grid
 of the faces (kernels.mesh_face_grid / mesh_nearest_faces), and mesh_distance(..., exact=True) measures the samples of
 each mesh against the surface of the other.
+
+RAY CASTING (csrc/mesh_raycast.hip) is the second query over that face grid: ray_cast_mesh returns,
+for every ray, the nearest face it hits, the ray's parameter there and the barycentric coordinates of the hit.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["nearest_points", "nearest_on_mesh", "point_set_metrics", "mesh_distance"]
+__all__ = ["nearest_points", "nearest_on_mesh", "ray_cast_mesh", "point_set_metrics", "mesh_distance"]
 
 DEFAULT_SAMPLES = 2 ** 18
 
@@ -131,6 +134,22 @@ def nearest_on_mesh(query, mesh, cell_size=None):
     K._finite_points(query, "query")
     grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)
     return K.mesh_nearest_faces(query, mesh.vertices, mesh.faces, grid, finite_checked=True)
+
+
+def ray_cast_mesh(rays, mesh, cell_size=None, cull_backfaces=False, grid=None):
+    """(t (n,) float64, face (n,) int32, bary (n,2) float32): for every row [o, d, near, far] of ``rays`` (n,8)
+    float32 the nearest face of ``mesh`` (a Mesh on the device) that the ray o + t d hits with near <= t <= far: t in
+    the ray's own parameter (d is not normalised), +inf on a miss; the face, the smallest index on equal t, -1 on a
+    miss; (u, v) with the hit point (1 - u - v) a + u b + v c, zeros on a miss; the result of testing every face, bit
+    for bit (kernels.mesh_ray_cast).  ``cull_backfaces``: only faces whose winding normal points
+    against the ray.  ``grid``: a kernels.mesh_face_grid of this mesh built before, to cast many ray sets through one
+    grid (``cell_size`` is then ignored); default: built here with ``cell_size``.  ValueError before any launch as
+    kernels.mesh_face_grid and kernels.mesh_ray_cast state."""
+    if grid is not None:
+        return K.mesh_ray_cast(rays, mesh.vertices, mesh.faces, grid, cull_backfaces)
+    K._rays_arg(rays)
+    grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)  # it checks the mesh
+    return K.mesh_ray_cast(rays, mesh.vertices, mesh.faces, grid, cull_backfaces, finite_checked=True)
 
 
 def _unit_face_normals(mesh):

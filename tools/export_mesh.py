@@ -34,6 +34,14 @@ With --exact every sample is measured against the other surface's triangles inst
 no floor at the sampling spacing) and the line carries "exact": true; without it the line is unchanged.
 
   python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --smooth 10 --report-error --out mesh.ply
+
+--report-depth VIEWS (off by default; the files and the other JSON lines are unchanged) prints one more JSON line that
+puts the exported mesh next to the field it came from, seen from VIEWS cameras of the synthetic scene at --image-size:
+Mesh.render's depth against render_image's.  The field sees a surface where acc > 0.5.  The line gives
+the share of pixels where both, only the mesh, only the field or neither see a surface, and the median and the 90th
+percentile of |depth_mesh - depth_field| over the pixels where both do.
+
+  python tools/export_mesh.py --train-steps 2000 --min-faces 200 --report-depth 4 --out mesh.ply
 """
 import argparse
 import json
@@ -79,6 +87,8 @@ def main():
     ap.add_argument("--error-samples", type=int, default=2 ** 18, help="points per surface for --report-error")
     ap.add_argument("--exact", action="store_true",
                     help="--report-error measures the samples against the other surface's triangles, not its samples")
+    ap.add_argument("--report-depth", type=int, default=0, metavar="VIEWS",
+                    help="also compare the exported mesh's depth with the field's from this many cameras")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -146,6 +156,43 @@ def main():
             print(json.dumps({"report_error": {"a": "exported", "b": "before simplify / smooth",
                                                "samples": a.error_samples, "lattice_spacing": h,
                                                **({"exact": True} if a.exact else {}), **err}}))
+    if a.report_depth:
+        print(json.dumps({"report_depth": depth_report(model, mesh, a.report_depth, a.image_size, a.samples)}))
+
+
+def depth_report(model, mesh, views, size, samples):
+    """The exported mesh against the field it came from, seen from ``views`` cameras of the synthetic scene
+    (scene.hemisphere_poses, near 2 / far 6, ``size`` x ``size`` pixels): Mesh.render's depth next to render_image's.
+    The field sees a surface where acc > 0.5, the mesh where a face is hit; both depths are in the ray parameter of
+    unit directions."""
+    import math
+
+    from nerf_amd.ray_rendering import render_image
+    from nerf_amd.scene import hemisphere_poses
+    focal = 0.5 * size / math.tan(0.5 * 0.6911112)  # make_blender_scene's
+    dev = mesh.vertices.device
+    cam = dict(H=size, W=size, fx=focal, fy=focal, cx=size / 2.0, cy=size / 2.0)
+    grid = None
+    both, only_mesh, only_field, neither, diffs = 0, 0, 0, 0, []
+    for c2w in hemisphere_poses(views, seed=0):
+        _, depth_field, acc = render_image(model, c2w=c2w, near=2.0, far=6.0, ray_samples=samples, **cam)
+        if mesh.faces.shape[0] and grid is None:
+            from nerf_amd import kernels as K
+            grid = K.mesh_face_grid(mesh.vertices, mesh.faces)
+        image = mesh.render(c2w=c2w.to(dev), near=2.0, far=6.0, grid=grid, **cam)
+        seen_mesh, seen_field = image["mask"].reshape(-1), acc > 0.5
+        both += int((seen_mesh & seen_field).sum())
+        only_mesh += int((seen_mesh & ~seen_field).sum())
+        only_field += int((~seen_mesh & seen_field).sum())
+        neither += int((~seen_mesh & ~seen_field).sum())
+        diffs.append((image["depth"].reshape(-1) - depth_field)[seen_mesh & seen_field].abs())
+    diffs = torch.cat(diffs).to(torch.float64)
+    n = float(views * size * size)
+    q = torch.quantile(diffs, torch.tensor([0.5, 0.9], dtype=torch.float64, device=diffs.device)).tolist() \
+        if diffs.numel() else [None, None]
+    return {"views": views, "image_size": size, "faces": int(mesh.faces.shape[0]), "both": both / n,
+            "only_mesh": only_mesh / n, "only_field": only_field / n, "neither": neither / n,
+            "depth_diff_median": q[0], "depth_diff_p90": q[1]}
 
 
 if __name__ == "__main__":
