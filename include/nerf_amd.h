@@ -849,6 +849,31 @@ int nerf_mesh_ray_cast(const float* rays, int64_t n, const int64_t* sorted_keys,
                        const int32_t* dims, double margin, int cull, double* t, int32_t* face, float* bary,
                        hipStream_t stream);
 
+/* Point-in-mesh by exact crossing counts through the face grid above, and uniform points of a box.
+ * query (n,3) float32 finite, vertices and faces as above: the kernels check none of it, the caller does.  The
+ * argument checks of nerf_mesh_ray_cast (without margin and cull): NERF_E_ARG, and NERF_E_ALIGN for sorted_keys, both
+ * before any launch.  No LDS, no atomics, one writer per output: equal inputs give equal bits.
+ * nerf_mesh_point_crossings: for every query q the faces crossed by the open vertical ray q + t e_z, t > 0:
+ *   crossings[i] = their number, winding[i] = the sum of their s (+1 inside a closed mesh whose normals point
+ *   outwards): the result of testing every face, bit for bit.  orient(P, Q, R) is the EXACT sign of
+ *   (Qx - Px)(Ry - Py) - (Qy - Py)(Rx - Px) (six exact double products of fp32 values, a floating filter
+ *   |sum| > 2^-48 sum |terms|, else a Shewchuk expansion).  Face (a, b, c) is crossed iff (1) in fp32, max z > qz and
+ *   qx, qy lie in [min, max] of the corners' x and y; (2) s = orient(a, b, c) != 0; (3) for each directed edge U -> V
+ *   of the projection taken counter-clockwise (b and c swapped when s < 0), e = orient(U, V, q) > 0, or e == 0 and
+ *   (Vy < Uy, or Vy == Uy and Vx > Ux): the query perturbed by (+eps, +eps^2), the same for every face; (4) in
+ *   rounded double, n = (b - a) x (c - a), g = (nx wx + ny wy) + nz wz of w = q - a: g < 0 and s > 0, or g > 0 and
+ *   s < 0.  The column of the query's cell is read from the query's own cell upwards; a face registered in several
+ *   of its cells is tested once (the argument: mesh_inside_core.hpp).  n_keys = 0: zeros.  One thread per query.
+ * nerf_box_points: points (n,3) float32, coordinate c of point i = lo_c + u (hi_c - lo_c) in fp32 (difference, product
+ *   and sum each rounded), u = (rand64(seed, 0x626f78 + c, i) >> 40) 2^-24 with the counter random numbers of
+ *   nerf_mesh_sample_surface: point i depends on (seed, i) and the box alone.  lo and hi are HOST arrays of 3 finite
+ *   floats with lo <= hi and a finite difference, else NERF_E_ARG.  One thread per point. */
+int nerf_mesh_point_crossings(const float* query, int64_t n, const int64_t* sorted_keys, int64_t n_keys,
+                              const float* vertices, const int32_t* faces, int64_t F, const float* lo, float cell,
+                              float inv, const int32_t* dims, int32_t* crossings, int32_t* winding,
+                              hipStream_t stream);
+int nerf_box_points(int64_t n, uint64_t seed, const float* lo, const float* hi, float* points, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -1140,6 +1140,91 @@ def mesh_ray_cast(rays, vertices, faces, grid, cull_backfaces=False, finite_chec
     return t, face, bary
 
 
+# ------------------------------------------------------------------ crossing counts
+
+
+def mesh_point_crossings(query, vertices, faces, grid, sort_queries=True, finite_checked=False):
+    """The faces crossed by the vertical ray from every query (nerf_mesh_point_crossings): query (n,3) float32, finite;
+    vertices and faces the mesh that ``grid`` = mesh_face_grid(vertices, faces) was built from.  Returns (crossings
+    (n,) int32, winding (n,) int32): the number of faces the open ray q + t e_z, t > 0, crosses and the sum of the signs
+    of their projected orientations (+1 inside a closed mesh whose normals point outwards); exactly what testing every
+    face gives, bit for bit.  Whether q's vertical line passes through a face's projection is decided exactly, with q
+    perturbed symbolically by (+eps, +eps^2), so a ray through a shared edge or a vertex of a closed mesh is counted
+    once per sheet; the side of the face's plane is decided in rounded double, so only a query within
+    rounding of the surface itself is unspecified, and even it is deterministic.  A vertical or degenerate face is never
+    crossed.  ``sort_queries``: present the queries in the order of their own cell keys (as points_nearest does); the
+    result is the same either way.  F == 0 or n == 0 gives zeros without a launch.  ValueError before any launch on
+    CPU tensors, wrong dtypes or shapes, non-finite queries or vertices, out-of-range indices and a grid that is not
+    the face grid of these faces.  Host reads: the finiteness of the queries and of the vertices and the index range,
+    all three skipped with ``finite_checked``."""
+    n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
+    V = _vertices_arg(vertices) if finite_checked else _finite_vertices(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
+    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
+        raise ValueError("grid must be the dict that mesh_face_grid returns")
+    n_keys = int(grid["n_keys"])
+    keys = grid["keys"]
+    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
+            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
+        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
+    if n_keys:
+        need(keys, "grid['keys']", torch.int64)
+    dev = query.device
+    if F == 0 or n == 0:
+        return torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+    crossings = torch.empty(n, dtype=torch.int32, device=dev)
+    winding = torch.empty(n, dtype=torch.int32, device=dev)
+    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
+    cell, inv = float(grid["cell"]), float(grid["inv"])
+    L = lib()
+
+    def run(q, out_c, out_w):
+        check(L.nerf_mesh_point_crossings(ptr(q), n, ptr(keys), n_keys, ptr(vertices), ptr(faces), F, lo_c, cell, inv,
+                                          dims_c, ptr(out_c), ptr(out_w), stream()), "nerf_mesh_point_crossings")
+
+    if not sort_queries:
+        run(query, crossings, winding)
+        return crossings, winding
+    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
+    sc, sw = torch.empty_like(crossings), torch.empty_like(winding)
+    run(_gather3(query, order), sc, sw)
+    order = order.to(torch.int64)
+    crossings[order] = sc
+    winding[order] = sw
+    return crossings, winding
+
+
+def box_points(n, lo, hi, seed=0, device=None):
+    """n points distributed uniformly over the box [lo, hi] (nerf_box_points): n an int in [0, 2^31); lo and hi 3 finite
+    floats each, taken as fp32, with lo <= hi and a finite difference; seed an int in [0, 2^64); ``device`` a HIP
+    device (default: the current one).  Returns (n,3) float32: coordinate c of point i is lo_c + u (hi_c - lo_c) in
+    fp32 with u a 24-bit counter random number of (seed, c, i) in [0, 1): point i depends on (seed, i) and the box
+    alone, bitwise reproducible, and a prefix of a longer run.  ValueError before the launch on a bad argument."""
+    import numpy as np
+    n, seed = _count_arg(n), _seed_arg(seed)
+    try:
+        with np.errstate(all="ignore"):
+            box = [np.asarray([float(x) for x in (b.reshape(-1).tolist() if isinstance(b, torch.Tensor) else b)],
+                              np.float32) for b in (lo, hi)]
+    except (TypeError, ValueError):
+        raise ValueError(f"lo and hi must be 3 floats each, got {lo!r} and {hi!r}") from None
+    with np.errstate(all="ignore"):
+        if box[0].shape != (3,) or box[1].shape != (3,) or not (np.isfinite(box[0]).all() and np.isfinite(box[1]).all()
+                                                               and (box[0] <= box[1]).all()
+                                                               and np.isfinite(box[1] - box[0]).all()):
+            raise ValueError(f"lo and hi must be 3 finite floats each with lo <= hi, got {lo!r} and {hi!r}")
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError("nerf_amd ops take HIP device tensors only (no CPU fallback)")
+    points = torch.empty((n, 3), dtype=F32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            check(lib().nerf_box_points(n, seed, (ctypes.c_float * 3)(*box[0].tolist()),
+                                        (ctypes.c_float * 3)(*box[1].tolist()), ptr(points), stream()),
+                  "nerf_box_points")
+    return points
+
+
 # ------------------------------------------------------------------ optimiser
 
 

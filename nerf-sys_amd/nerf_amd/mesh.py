@@ -340,6 +340,41 @@ class Mesh:
         from .mesh_metrics import ray_cast_mesh
         return ray_cast_mesh(rays, self, cell_size=cell_size, cull_backfaces=cull_backfaces, grid=grid)
 
+    # ---- containment on the device (kernels.mesh_point_crossings)
+
+    def contains(self, points, rule="parity", cell_size=None, grid=None):
+        """mesh_metrics.points_in_mesh(points, self, ...): (n,) bool, whether every row of ``points`` (n,3) float32 lies
+        inside this mesh, by the parity of the faces the vertical ray from the point crosses (``rule`` = "winding":
+        by their winding number).  Exact except within rounding of the surface; meaningful for a closed mesh only."""
+        from .mesh_metrics import points_in_mesh
+        return points_in_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid)
+
+    def signed_distance(self, points, rule="parity", cell_size=None, grid=None):
+        """mesh_metrics.signed_distance_to_mesh(points, self, ...): (sd (n,) float64, face (n,) int32, closest (n,3)
+        float32), the distance of closest_points with a negative sign inside; meaningful for a closed mesh only."""
+        from .mesh_metrics import signed_distance_to_mesh
+        return signed_distance_to_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid)
+
+    def volume(self) -> float:
+        """The signed volume: the float64 torch sum of a . (b x c) / 6 over the faces (the divergence theorem).
+        Positive for a closed mesh whose normals point outwards, which is the extractor's convention.  For an open
+        mesh it means nothing: the value then depends on where the origin lies.  ValueError on out-of-range indices."""
+        K._faces_arg(self.faces, K._vertices_arg(self.vertices))
+        if self.faces.shape[0] == 0:
+            return 0.0
+        p = self.vertices.to(torch.float64)
+        f = self.faces.to(torch.int64)
+        a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+        return float((a * torch.linalg.cross(b, c)).sum() / 6.0)
+
+    def iou(self, other, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None) -> dict:
+        """mesh_metrics.volume_iou(self, other, ...): the Monte Carlo volumetric intersection over union of two closed
+        meshes and the volumes it rests on, as a dict with self as a and other as b."""
+        from .mesh_metrics import volume_iou
+        if not isinstance(other, Mesh):
+            raise ValueError(f"other must be a Mesh, got {type(other).__name__}")
+        return volume_iou(self, other, n_samples=n_samples, seed=seed, rule=rule, cell_size=cell_size)
+
     def render(self, H, W, fx, fy, cx, cy, c2w, near=0.0, far=float("inf"), cull_backfaces=False, grid=None) -> dict:
         """The mesh seen from a pinhole camera, through the rays of ray_sampling.rays_for_camera (pixel centres, the
         camera looking along its -z axis, unit directions): a dict of device tensors,

@@ -17,6 +17,11 @@ each mesh against the surface of the other.
 
 RAY CASTING (csrc/mesh_raycast.hip) is the second query over that face grid: ray_cast_mesh returns,
 for every ray, the nearest face it hits, the ray's parameter there and the barycentric coordinates of the hit.
+
+CONTAINMENT (csrc/mesh_inside.hip) is the third: points_in_mesh counts the faces the vertical ray from
+a query crosses, with an exact in-projection test, and from it come signed_distance_to_mesh (the sign for
+nearest_on_mesh's magnitude) and volume_iou (Monte Carlo over kernels.box_points).  All three mean something for a
+closed mesh only.
 """
 from __future__ import annotations
 
@@ -26,7 +31,8 @@ import torch
 
 from . import kernels as K
 
-__all__ = ["nearest_points", "nearest_on_mesh", "ray_cast_mesh", "point_set_metrics", "mesh_distance"]
+__all__ = ["nearest_points", "nearest_on_mesh", "ray_cast_mesh", "point_set_metrics", "mesh_distance",
+           "points_in_mesh", "signed_distance_to_mesh", "volume_iou"]
 
 DEFAULT_SAMPLES = 2 ** 18
 
@@ -150,6 +156,87 @@ def ray_cast_mesh(rays, mesh, cell_size=None, cull_backfaces=False, grid=None):
     K._rays_arg(rays)
     grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)  # it checks the mesh
     return K.mesh_ray_cast(rays, mesh.vertices, mesh.faces, grid, cull_backfaces, finite_checked=True)
+
+
+def _rule_arg(rule):
+    if rule not in ("parity", "winding"):
+        raise ValueError(f"rule must be 'parity' or 'winding', got {rule!r}")
+    return rule
+
+
+def _inside(crossings, winding, rule):
+    return (crossings & 1).to(torch.bool) if rule == "parity" else winding != 0
+
+
+def points_in_mesh(query, mesh, rule="parity", cell_size=None, grid=None):
+    """(n,) bool: whether every row of ``query`` (n,3) float32 lies inside ``mesh`` (a Mesh on the device), from the
+    faces the vertical ray from the query crosses (kernels.mesh_point_crossings).  ``rule``: "parity",
+    an odd number of crossings, or "winding", a non-zero sum of the crossed faces' orientations (it tells a doubly
+    covered region from an empty one; for a closed mesh without self-intersections both agree).  The answer means
+    something for a CLOSED mesh only; an extracted surface is open where it meets its box.  Exact except within
+    rounding of the surface itself.  ``grid``: a kernels.mesh_face_grid of this mesh built before (``cell_size`` is then
+    ignored); default: built here with ``cell_size``.  A mesh without faces contains nothing.  ValueError before any
+    launch on a bad rule and as kernels.mesh_face_grid and kernels.mesh_point_crossings state."""
+    _rule_arg(rule)
+    if grid is not None:
+        return _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid), rule)
+    K._finite_points(query, "query")
+    grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)  # it checks the mesh
+    return _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid, finite_checked=True), rule)
+
+
+def signed_distance_to_mesh(query, mesh, rule="parity", cell_size=None, grid=None):
+    """(sd (n,) float64, face (n,) int32, closest (n,3) float32): nearest_on_mesh's face and closest point, and the
+    distance sqrt(d2) with the sign of points_in_mesh: negative inside, positive outside, +0.0 where d2 == 0.  One face
+    grid serves both queries (``grid``: one built before; ``cell_size`` is then ignored).  The sign is that of a
+    CLOSED mesh (see points_in_mesh); no pseudo-normals are involved.  A mesh without faces gives +inf, -1 and the
+    query itself.  ValueError before any launch as points_in_mesh."""
+    _rule_arg(rule)
+    checked = grid is None
+    if checked:
+        K._finite_points(query, "query")
+        grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)  # it checks the mesh
+    d2, face, closest = K.mesh_nearest_faces(query, mesh.vertices, mesh.faces, grid, finite_checked=checked)
+    inside = _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid, finite_checked=True), rule)
+    d = torch.sqrt(d2)
+    return torch.where(inside & (d2 > 0), -d, d), face, closest
+
+
+def volume_iou(mesh_a, mesh_b, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None):
+    """The volumetric intersection over union of two CLOSED meshes by Monte Carlo: ``n_samples`` kernels.box_points of
+    the common box of both meshes' vertices, each tested with points_in_mesh against either mesh.  Returns a dict:
+    iou = intersection / union (0.0 when the union is empty); volume_a, volume_b, intersection, union = the count
+    times box volume / n_samples; count_a, count_b, count_intersection, count_union the four raw counts; n_samples; box
+    = (lo, hi), the fp32 corners as lists.  The standard error of a volume is box volume sqrt(p (1 - p) / n_samples)
+    for its share p.  Equal arguments give equal dicts (the points and the counts are bitwise reproducible).  Host
+    reads: the checks of both meshes, the two grids', the box, and one for the four counts.  ValueError before any launch on n_samples < 1, a bad
+    seed or rule, a mesh without faces, and as kernels.mesh_face_grid states."""
+    K._count_arg(n_samples, "n_samples")
+    if n_samples < 1:
+        raise ValueError(f"n_samples must be >= 1, got {n_samples!r}")
+    K._seed_arg(seed)
+    _rule_arg(rule)
+    if cell_size is not None:
+        K._cell_size_arg(cell_size)
+    for m in (mesh_a, mesh_b):  # both meshes before the first grid's launches
+        K._faces_arg(m.faces, K._finite_vertices(m.vertices))
+        if m.faces.shape[0] == 0:
+            raise ValueError("volume_iou needs meshes with faces")
+    grid_a = K.mesh_face_grid(mesh_a.vertices, mesh_a.faces, cell_size)
+    grid_b = K.mesh_face_grid(mesh_b.vertices, mesh_b.faces, cell_size)
+    both = torch.cat([mesh_a.vertices, mesh_b.vertices])
+    box = torch.cat([both.amin(0), both.amax(0)]).tolist()
+    lo, hi = box[:3], box[3:]
+    points = K.box_points(n_samples, lo, hi, seed=seed, device=mesh_a.vertices.device)
+    ia = _inside(*K.mesh_point_crossings(points, mesh_a.vertices, mesh_a.faces, grid_a, finite_checked=True), rule)
+    ib = _inside(*K.mesh_point_crossings(points, mesh_b.vertices, mesh_b.faces, grid_b, finite_checked=True), rule)
+    counts = torch.stack([ia.sum(), ib.sum(), (ia & ib).sum(), (ia | ib).sum()]).tolist()  # one host read
+    scale = ((hi[0] - lo[0]) * (hi[1] - lo[1])) * (hi[2] - lo[2]) / n_samples
+    out = dict(zip(("volume_a", "volume_b", "intersection", "union"), (c * scale for c in counts)))
+    out.update(zip(("count_a", "count_b", "count_intersection", "count_union"), counts))
+    out["iou"] = counts[2] / counts[3] if counts[3] else 0.0
+    out["n_samples"], out["box"] = n_samples, (lo, hi)
+    return out
 
 
 def _unit_face_normals(mesh):

@@ -35,6 +35,14 @@ no floor at the sampling spacing) and the line carries "exact": true; without it
 
   python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --smooth 10 --report-error --out mesh.ply
 
+--report-iou (off by default; the files and the other JSON lines are unchanged) prints one more JSON line for the same
+pair as --report-error, the exported mesh (a) and the surface before --simplify / --smooth (b): Mesh.iou (DESIGN
+§3.11.7), the Monte Carlo volumetric intersection over union from --iou-samples points of their common box, and both
+Mesh.volume() values.  All of it means something where the surfaces are closed; a surface that meets the box of the
+extraction is open there.
+
+  python tools/export_mesh.py --train-steps 2000 --keep-largest 1 --simplify 0.02 --report-iou --out mesh.ply
+
 --report-depth VIEWS (off by default; the files and the other JSON lines are unchanged) prints one more JSON line that
 puts the exported mesh next to the field it came from, seen from VIEWS cameras of the synthetic scene at --image-size:
 Mesh.render's depth against render_image's.  The field sees a surface where acc > 0.5.  The line gives
@@ -87,6 +95,9 @@ def main():
     ap.add_argument("--error-samples", type=int, default=2 ** 18, help="points per surface for --report-error")
     ap.add_argument("--exact", action="store_true",
                     help="--report-error measures the samples against the other surface's triangles, not its samples")
+    ap.add_argument("--report-iou", action="store_true",
+                    help="also print the volumetric IoU of the exported mesh and the surface before --simplify / --smooth")
+    ap.add_argument("--iou-samples", type=int, default=2 ** 20, help="points of the common box for --report-iou")
     ap.add_argument("--report-depth", type=int, default=0, metavar="VIEWS",
                     help="also compare the exported mesh's depth with the field's from this many cameras")
     ap.add_argument("--out", default="mesh.ply")
@@ -156,6 +167,15 @@ def main():
             print(json.dumps({"report_error": {"a": "exported", "b": "before simplify / smooth",
                                                "samples": a.error_samples, "lattice_spacing": h,
                                                **({"exact": True} if a.exact else {}), **err}}))
+    if a.report_iou:
+        before = model.extract_mesh(resolution=a.resolution, threshold=a.threshold, normals=None,
+                                    min_faces=a.min_faces, keep_largest=a.keep_largest)
+        if mesh.faces.shape[0] == 0 or before.faces.shape[0] == 0:
+            print(json.dumps({"report_iou": None, "reason": "a surface without faces encloses nothing"}))
+        else:
+            print(json.dumps({"report_iou": {"a": "exported", "b": "before simplify / smooth",
+                                             "mesh_volume_a": mesh.volume(), "mesh_volume_b": before.volume(),
+                                             **mesh.iou(before, n_samples=a.iou_samples)}}))
     if a.report_depth:
         print(json.dumps({"report_depth": depth_report(model, mesh, a.report_depth, a.image_size, a.samples)}))
 
