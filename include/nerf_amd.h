@@ -874,6 +874,31 @@ int nerf_mesh_point_crossings(const float* query, int64_t n, const int64_t* sort
                               hipStream_t stream);
 int nerf_box_points(int64_t n, uint64_t seed, const float* lo, const float* hi, float* points, hipStream_t stream);
 
+/* TSDF fusion of depth views.  The volume is the lattice of nerf_mesh_emit: tsdf and weight
+ * (nx,ny,nz) contiguous fp32, p = (ix ny + iy) nz + iz, the point x = lo + (ix,iy,iz) h, h = (hi - lo) / (n - 1);
+ * every dimension >= 2 and nx ny nz < 2^31, lo / hi HOST arrays of 3 floats with lo < hi (else NERF_E_ARG).  A fresh
+ * volume holds tsdf = 1, weight = 0.  Everything is fp32 and every operation is rounded once.
+ * nerf_tsdf_integrate: c2w (n_views,12) rows of the 3x4 camera-to-world matrices of nerf_rays_gen, depth
+ *   (n_views,H,W) ranges along unit ray directions (the depth of Mesh.render / render_image), indexed in int64; one
+ *   fx, fy, cx, cy and trunc for the launch: trunc, fx, fy finite and > 0, cx, cy finite, 1 <= H, W <= 2^24 (else
+ *   NERF_E_ARG).  Per voxel, the views in ascending order (n views in one launch are bit for bit n launches of one):
+ *   q = x - o, o = (M[3], M[7], M[11]); c_j = q0 M[j] + q1 M[4+j] + q2 M[8+j]; zc = -c_2, skip unless zc > 0;
+ *   u = fx (c_0 / zc) + cx, v = fy ((-c_1) / zc) + cy, skip unless 0 <= u < W and 0 <= v < H (in float; NaN skips);
+ *   d = depth[view, floor(v), floor(u)], skip unless d is finite and > 0; r = sqrt(q0 q0 + q1 q1 + q2 q2),
+ *   s = d - r, skip if s < -trunc; t = min(1, s / trunc); tsdf = (tsdf w + t) / (w + 1), w = w + 1.  A voxel that
+ *   no view updated is not written.  n_views = 0 launches nothing.  One thread per voxel, no atomics; at most 8
+ *   views per launch, the launches of a call one after the other on the stream (the same bits as one launch).  c2w must be
+ *   finite; the kernel does not check.
+ * nerf_tsdf_face_observed: face_off (nx ny nz + 1) = the exclusive scan nerf_mesh_emit took, F its total
+ *   (0 <= F <= 12 nx ny nz); keep[f] = 1 iff all 8 corners of the cell that owns face f have weight >= min_weight,
+ *   else 0, for f in [face_off[p], face_off[p+1]) of every point p (a slot outside [0, F) is not written).  F = 0
+ *   launches nothing.  One thread per lattice point. */
+int nerf_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* lo, const float* hi,
+                        const float* depth, const float* c2w, int n_views, int H, int W, float fx, float fy, float cx,
+                        float cy, float trunc, hipStream_t stream);
+int nerf_tsdf_face_observed(const int32_t* face_off, const float* weight, int nx, int ny, int nz, float min_weight,
+                            int64_t F, uint8_t* keep, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

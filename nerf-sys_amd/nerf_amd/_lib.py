@@ -175,6 +175,8 @@ def lib():
             "nerf_mesh_ray_cast": [P, I64, P, I64, P, P, I64, P, F, F, P, D, I, P, P, P, P],
             "nerf_mesh_point_crossings": [P, I64, P, I64, P, P, I64, P, F, F, P, P, P, P],
             "nerf_box_points": [I64, U64, P, P, P, P],
+            "nerf_tsdf_integrate": [P, P, I, I, I, P, P, P, P, I, I, I, F, F, F, F, F, P],
+            "nerf_tsdf_face_observed": [P, P, I, I, I, F, I64, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -241,7 +243,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_vertex_normals",
            "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",
            "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces",
-           "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points")
+           "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points",
+           "nerf_tsdf_integrate", "nerf_tsdf_face_observed")
 
 
 def check(status: int, what: str) -> None:

@@ -323,12 +323,14 @@ def _box3(v, name):
     return v
 
 
-def mesh_extract(field, iso, lo, hi, normals=False):
+def mesh_extract(field, iso, lo, hi, normals=False, face_offsets=False):
     """Marching tetrahedra (nerf_mesh_classify -> two scans -> nerf_mesh_emit): field (nx,ny,nz) float32, finite, every
     dimension >= 2, sampled at lo + (ix,iy,iz) (hi - lo) / (n - 1); inside iff field > iso.  Returns verts (V,3)
     float32 and faces (F,3) int32 (welded: one vertex per crossing lattice edge; face normals towards lower values),
-    and with ``normals`` the unit normals (V,3) of the lattice's central-difference gradient.  Two host reads: the
-    finiteness check and the two totals that size the outputs.  Bitwise reproducible (no atomics)."""
+    and with ``normals`` the unit normals (V,3) of the lattice's central-difference gradient.  With ``face_offsets``
+    the tuple gains, as its last element, face_off (nx ny nz + 1,) int32: the faces of the cell with low corner p are
+    [face_off[p], face_off[p+1]).  Two host reads: the finiteness check and the two totals that size the outputs.
+    Bitwise reproducible (no atomics)."""
     from .occupancy import exclusive_scan
     need(field, "field")
     if field.dim() != 3:
@@ -358,7 +360,102 @@ def mesh_extract(field, iso, lo, hi, normals=False):
     check(lib().nerf_mesh_emit(ptr(field), nx, ny, nz, float(iso), lo_c, hi_c, ptr(mask), ptr(voff), ptr(foff), V, F,
                                ptr(verts) if V else None, ptr(faces) if F else None,
                                ptr(nrm) if normals and V else None, stream()), "nerf_mesh_emit")
-    return (verts, faces, nrm) if normals else (verts, faces)
+    out = (verts, faces, nrm) if normals else (verts, faces)
+    return out + (foff,) if face_offsets else out
+
+
+# ------------------------------------------------------------------ TSDF fusion of depth views
+
+
+def _volume_arg(t, name, shape=None):
+    need(t, name)
+    if t.dim() != 3 or min(t.shape) < 2:
+        raise ValueError(f"{name} must be (nx,ny,nz) with every dimension >= 2, got {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    if t.numel() >= 2 ** 31:
+        raise ValueError(f"lattice too large: {t.numel()} points reaches 2^31")
+    return tuple(int(n) for n in t.shape)
+
+
+def _f32_arg(v, name, positive):
+    """v as a finite (and positive) fp32, else ValueError"""
+    try:
+        f = float(torch.tensor(float(v), dtype=F32))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name} must be a number, got {v!r}") from None
+    if f != f or f in (float("inf"), float("-inf")) or (positive and not f > 0.0):
+        raise ValueError(f"{name} must be a finite{' positive' if positive else ''} float32, got {v!r}")
+    return f
+
+
+def tsdf_integrate(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy, trunc):
+    """Fuse depth views into a truncated signed distance volume, in place (nerf_tsdf_integrate, one launch per 8 views):
+    tsdf and
+    weight (nx,ny,nz) float32 over the lattice of mesh_extract; depth (n,H,W) or (H,W) float32, ranges along unit ray
+    directions (render_image's depth over acc, Mesh.render's depth: +inf, NaN, 0 and negative values are "no surface");
+    c2w (n,3,4), (n,4,4), (3,4) or (4,4) float32, finite, the cameras of rays_gen.  Per voxel and view, in the order of
+    the views: project to the pixel that holds the voxel, s = depth - range of the voxel, skip if s < -trunc, else
+    tsdf = (tsdf w + min(1, s / trunc)) / (w + 1), w += 1 (DESIGN §3.11.8 states every step).  n views in one call
+    are bit for bit n calls of one view.  Returns nothing.  One host read: the finiteness of c2w."""
+    shape = _volume_arg(tsdf, "tsdf")
+    _volume_arg(weight, "weight", shape)
+    if tsdf.device != weight.device:
+        raise ValueError("tsdf and weight must be on one device")
+    lo, hi = _box3(lo, "lo"), _box3(hi, "hi")
+    if not all(a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"lo must be below hi on every axis, got {lo} vs {hi}")
+    need(depth, "depth")
+    need(c2w, "c2w")
+    if depth.device != tsdf.device or c2w.device != tsdf.device:
+        raise ValueError("depth and c2w must be on the volume's device")
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3 or (depth.shape[0] and min(depth.shape[1:]) < 1):
+        raise ValueError(f"depth must be (n,H,W) or (H,W) with H, W >= 1, got {tuple(depth.shape)}")
+    if c2w.dim() == 2:
+        c2w = c2w[None]
+    if c2w.dim() != 3 or tuple(c2w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"c2w must be (n,3,4), (n,4,4), (3,4) or (4,4), got {tuple(c2w.shape)}")
+    n, H, W = (int(v) for v in depth.shape)
+    if max(H, W) > 2 ** 24:
+        raise ValueError(f"H and W must be at most 2^24, got {H}, {W}")
+    if c2w.shape[0] != n:
+        raise ValueError(f"depth holds {n} views, c2w {c2w.shape[0]}")
+    fx, fy = _f32_arg(fx, "fx", True), _f32_arg(fy, "fy", True)
+    cx, cy = _f32_arg(cx, "cx", False), _f32_arg(cy, "cy", False)
+    trunc = _f32_arg(trunc, "trunc", True)
+    if n == 0:
+        return
+    rows = c2w[:, :3, :].contiguous()
+    if not bool(torch.isfinite(rows).all()):
+        raise ValueError("c2w must be finite")
+    lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    check(lib().nerf_tsdf_integrate(ptr(tsdf), ptr(weight), *shape, lo_c, hi_c, ptr(depth), ptr(rows), n, H, W, fx, fy,
+                                    cx, cy, trunc, stream()), "nerf_tsdf_integrate")
+
+
+def tsdf_face_observed(face_off, weight, min_weight):
+    """keep (F,) uint8 for the faces of mesh_extract(..., face_offsets=True) over the lattice of ``weight``
+    (nx,ny,nz) float32: 1 iff every one of the 8 corners of the face's cell has weight >= min_weight
+    (nerf_tsdf_face_observed).  face_off (nx ny nz + 1,) int32.  One host read: F = face_off[-1]."""
+    shape = _volume_arg(weight, "weight")
+    need(face_off, "face_off", torch.int32)
+    P = shape[0] * shape[1] * shape[2]
+    if tuple(face_off.shape) != (P + 1,):
+        raise ValueError(f"face_off must be ({P + 1},), got {tuple(face_off.shape)}")
+    if face_off.device != weight.device:
+        raise ValueError("face_off and weight must be on one device")
+    min_weight = float(min_weight)
+    if min_weight != min_weight:
+        raise ValueError("min_weight must not be NaN")
+    F = int(face_off[-1])
+    if F < 0 or F > 12 * P:
+        raise ValueError(f"face_off is no scan of face counts: its total is {F}")
+    keep = torch.zeros(F, dtype=torch.uint8, device=weight.device)
+    check(lib().nerf_tsdf_face_observed(ptr(face_off), ptr(weight), *shape, min_weight, F, ptr(keep) if F else None,
+                                        stream()), "nerf_tsdf_face_observed")
+    return keep
 
 
 # ------------------------------------------------------------------ mesh clean-up (DESIGN §3.11.1)

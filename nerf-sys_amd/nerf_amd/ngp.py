@@ -818,6 +818,34 @@ class InstantNGP(nn.Module):
                             normals="grid" if normals == "grid" else None, chunk=chunk,
                             device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest,
                             simplify=simplify, smooth=smooth)
+        return self._mesh_attributes(mesh, normals, colors, params, chunk)
+
+    def extract_mesh_tsdf(self, poses, H, W, fx, fy, cx, cy, near, far, resolution=256, aabb=None, trunc=None,
+                          acc_min: float = 0.5, min_weight=1, normals="field", colors=None, min_faces=None,
+                          keep_largest=None, simplify=None, smooth=None, params=None, chunk: int = 2 ** 20,
+                          batch: int = 8, **render_kwargs):
+        """The surface the cameras ``poses`` (n,3,4) see, as a mesh.Mesh on the device: render_image's depth from every
+        pose, fused into a TSDF volume of ``resolution`` points over ``aabb`` (default: the model's box) by
+        ray_rendering.fuse_depth_views (trunc, acc_min, batch, render_kwargs as there), then
+        TSDFVolume.extract_mesh (min_weight, min_faces / keep_largest, simplify, smooth as there).  normals and colors
+        as in extract_mesh: field normals and colours are evaluated at the surviving vertices."""
+        from .ray_rendering import fuse_depth_views
+        if normals not in ("field", "grid", None):
+            raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
+        if colors not in (None, "linear", "srgb"):
+            raise ValueError(f"colors must be None, 'linear' or 'srgb', got {colors!r}")
+        box = self._aabb_host if aabb is None else [float(v) for v in torch.as_tensor(aabb).reshape(-1).tolist()]
+        if len(box) != 6:
+            raise ValueError(f"aabb must hold 6 floats (min, max), got {len(box)}")
+        vol = fuse_depth_views(self, poses, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, near=near, far=far, lo=box[:3],
+                               hi=box[3:], resolution=resolution, trunc=trunc, acc_min=acc_min, batch=batch,
+                               params=params, **render_kwargs)
+        mesh = vol.extract_mesh(min_weight=min_weight, normals="grid" if normals == "grid" else None,
+                                min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth)
+        return self._mesh_attributes(mesh, normals, colors, params, chunk)
+
+    def _mesh_attributes(self, mesh, normals, colors, params, chunk):
+        """field normals and colours at the vertices of ``mesh`` (extract_mesh, extract_mesh_tsdf)"""
         v = mesh.vertices
         field_nrm = None
         if normals == "field" or colors is not None:

@@ -1,0 +1,81 @@
+"""TSDF fusion: depth views fused into a truncated signed distance volume on the device (kernels.tsdf_integrate,
+csrc/tsdf.hip), and its zero level as a Mesh.
+
+The surface a set of cameras saw, not a level set of the density: depth images (ray_rendering.render_image's depth over
+acc, or Mesh.render's depth) are fused view by view; the zero level of the fused field is meshed by
+kernels.mesh_extract, and the triangles of cells that no view fully observed are dropped (kernels.tsdf_face_observed),
+which removes the sheet at -trunc behind every surface and everything the cameras never looked at.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from .mesh import Mesh, _box, _resolution
+
+__all__ = ["TSDFVolume"]
+
+
+class TSDFVolume:
+    """tsdf and weight (nx,ny,nz) float32 on the device over the lattice lo + (ix,iy,iz) spacing,
+    spacing = (hi - lo) / (n - 1) in fp32 (mesh_extract's lattice).  A fresh volume holds tsdf = 1 (free space) and
+    weight = 0; weight counts the views that updated a voxel.  trunc: the truncation distance in world units, default
+    3 x the largest axis spacing."""
+
+    def __init__(self, lo, hi, resolution: Union[int, Sequence[int]], trunc: Optional[float] = None, device=None):
+        self.lo, self.hi = _box(lo, hi)
+        self.resolution = _resolution(resolution)
+        if self.resolution[0] * self.resolution[1] * self.resolution[2] >= 2 ** 31:
+            raise ValueError(f"lattice too large: {self.resolution} reaches 2^31 points")
+        lo32, hi32 = np.asarray(self.lo, np.float32), np.asarray(self.hi, np.float32)
+        self.spacing = tuple(float((hi32[a] - lo32[a]) / np.float32(self.resolution[a] - 1)) for a in range(3))
+        if trunc is None:
+            trunc = float(np.float32(3.0) * np.float32(max(self.spacing)))
+        self.trunc = K._f32_arg(trunc, "trunc", True)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.tsdf = torch.empty(self.resolution, dtype=torch.float32, device=self.device)
+        self.weight = torch.empty(self.resolution, dtype=torch.float32, device=self.device)
+        self.reset()
+
+    def __repr__(self):
+        return f"TSDFVolume(resolution={self.resolution}, trunc={self.trunc:.6g}, device={self.device})"
+
+    def reset(self) -> None:
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+
+    def integrate(self, depth, fx, fy, cx, cy, c2w) -> None:
+        """Fuse depth (n,H,W) or (H,W) seen from c2w (n,3,4), (n,4,4), (3,4) or (4,4) in one call
+        (kernels.tsdf_integrate): ranges along unit ray directions; +inf, NaN, 0 and negative values see nothing."""
+        if not isinstance(depth, torch.Tensor) or not isinstance(c2w, torch.Tensor):
+            raise ValueError("depth and c2w must be tensors")
+        K.tsdf_integrate(self.tsdf, self.weight, self.lo, self.hi, depth, c2w, fx, fy, cx, cy, self.trunc)
+
+    def extract_mesh(self, min_weight=1, normals: Optional[str] = "grid", min_faces: Optional[int] = None,
+                     keep_largest: Optional[int] = None, simplify: Optional[float] = None,
+                     smooth: Optional[int] = None) -> Mesh:
+        """The zero level of the fused field as a Mesh: mesh_extract(-tsdf, 0) (inside is tsdf < 0, normals point to
+        larger tsdf: outwards), then only the faces of cells whose 8 corners all have weight >= min_weight
+        (min_weight = 0 keeps every face, the sheet at -trunc behind the surface included), then the options of
+        mesh.extract_mesh in its order: min_faces / keep_largest (at most one), simplify, smooth."""
+        if normals not in ("grid", None):
+            raise ValueError(f"normals must be 'grid' or None, got {normals!r}")
+        if smooth is not None and (isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0):
+            raise ValueError(f"smooth must be None or an int >= 0, got {smooth!r}")
+        if min_faces is not None and keep_largest is not None:
+            raise ValueError("give at most one of min_faces and keep_largest")
+        *parts, face_off = K.mesh_extract(-self.tsdf, 0.0, self.lo, self.hi, normals=(normals == "grid"),
+                                          face_offsets=True)
+        mesh = Mesh(*parts)
+        if float(min_weight) > 0.0:
+            mesh = mesh.select_faces(K.tsdf_face_observed(face_off, self.weight, min_weight))
+        if min_faces is not None or keep_largest is not None:
+            mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
+        if simplify is not None:
+            mesh = mesh.simplify(simplify)
+        if smooth is not None:
+            mesh = mesh.smooth(smooth)
+        return mesh

@@ -50,6 +50,15 @@ the share of pixels where both, only the mesh, only the field or neither see a s
 percentile of |depth_mesh - depth_field| over the pixels where both do.
 
   python tools/export_mesh.py --train-steps 2000 --min-faces 200 --report-depth 4 --out mesh.ply
+
+--tsdf VIEWS (off by default; the files and every JSON line are unchanged without it) exports the surface that VIEWS
+cameras of the synthetic scene see instead of the density level set: InstantNGP.extract_mesh_tsdf
+renders depth from scene.hemisphere_poses(VIEWS) at --image-size, fuses it into a TSDF volume of --resolution points and
+meshes the zero level; --threshold is then unused.  --tsdf-min-weight is the number of views every corner of a cell
+needs for its faces to be kept.  Every option and report above works on it; the first JSON line gains "tsdf" and
+"tsdf_min_weight".
+
+  python tools/export_mesh.py --train-steps 2000 --tsdf 32 --report-depth 4 --out mesh.ply
 """
 import argparse
 import json
@@ -100,6 +109,10 @@ def main():
     ap.add_argument("--iou-samples", type=int, default=2 ** 20, help="points of the common box for --report-iou")
     ap.add_argument("--report-depth", type=int, default=0, metavar="VIEWS",
                     help="also compare the exported mesh's depth with the field's from this many cameras")
+    ap.add_argument("--tsdf", type=int, default=0, metavar="VIEWS",
+                    help="export the TSDF fusion of the depth of this many cameras instead of the density level set")
+    ap.add_argument("--tsdf-min-weight", type=float, default=1.0,
+                    help="--tsdf keeps the faces of cells whose corners were all updated by this many views")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -128,13 +141,25 @@ def main():
         print(f"trained {a.train_steps} steps, loss {float(loss):.5f}" if a.train_steps else "untrained", file=sys.stderr)
         if a.save_checkpoint:
             torch.save(model.state_dict(), a.save_checkpoint)
+    if a.tsdf:
+        import math
+
+        from nerf_amd.scene import hemisphere_poses
+        size = a.image_size
+        focal = 0.5 * size / math.tan(0.5 * 0.6911112)  # make_blender_scene's
+        poses = hemisphere_poses(a.tsdf, seed=0)
+
+        def extract(**kw):
+            return model.extract_mesh_tsdf(poses, size, size, focal, focal, size / 2.0, size / 2.0, 2.0, 6.0,
+                                           resolution=a.resolution, min_weight=a.tsdf_min_weight,
+                                           ray_samples=a.samples, **kw)
+    else:
+        def extract(**kw):
+            return model.extract_mesh(resolution=a.resolution, threshold=a.threshold, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    mesh = model.extract_mesh(resolution=a.resolution, threshold=a.threshold,
-                              normals=None if a.normals == "none" else a.normals,
-                              colors=None if a.colors == "none" else a.colors,
-                              min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify,
-                              smooth=a.smooth)
+    mesh = extract(normals=None if a.normals == "none" else a.normals, colors=None if a.colors == "none" else a.colors,
+                   min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify, smooth=a.smooth)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mesh.save_ply(a.out)
@@ -142,8 +167,7 @@ def main():
         mesh.save_obj(a.obj)
     # for the report only (outside the timed call): the unfiltered surface and its components
     filtered = a.min_faces is not None or a.keep_largest is not None
-    full = mesh if not filtered and a.simplify is None else model.extract_mesh(
-        resolution=a.resolution, threshold=a.threshold, normals=None)
+    full = mesh if not filtered and a.simplify is None else extract(normals=None)
     n_components = int((full.components()[1] > 0).sum())
     after_filter = mesh if a.simplify is None else (
         full.filter_components(min_faces=a.min_faces, keep_largest=a.keep_largest) if filtered else full)
@@ -154,11 +178,11 @@ def main():
                       "faces_after_filter": int(after_filter.faces.shape[0]), "simplify": a.simplify,
                       "smooth": a.smooth,
                       "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
-                      "extract_seconds": round(dt, 4), "out": a.out}))
+                      "extract_seconds": round(dt, 4), "out": a.out,
+                      **({"tsdf": a.tsdf, "tsdf_min_weight": a.tsdf_min_weight} if a.tsdf else {})}))
     if a.report_error:
         # the surface the clustering and the smoothing started from: extracted again, filtered, nothing else
-        before = model.extract_mesh(resolution=a.resolution, threshold=a.threshold, normals=None,
-                                    min_faces=a.min_faces, keep_largest=a.keep_largest)
+        before = extract(normals=None, min_faces=a.min_faces, keep_largest=a.keep_largest)
         h = (AABB[1][0] - AABB[0][0]) / (a.resolution - 1)
         if mesh.faces.shape[0] == 0 or before.faces.shape[0] == 0:
             print(json.dumps({"report_error": None, "reason": "a surface without faces has no samples"}))
@@ -168,8 +192,7 @@ def main():
                                                "samples": a.error_samples, "lattice_spacing": h,
                                                **({"exact": True} if a.exact else {}), **err}}))
     if a.report_iou:
-        before = model.extract_mesh(resolution=a.resolution, threshold=a.threshold, normals=None,
-                                    min_faces=a.min_faces, keep_largest=a.keep_largest)
+        before = extract(normals=None, min_faces=a.min_faces, keep_largest=a.keep_largest)
         if mesh.faces.shape[0] == 0 or before.faces.shape[0] == 0:
             print(json.dumps({"report_iou": None, "reason": "a surface without faces encloses nothing"}))
         else:
