@@ -11,11 +11,15 @@
 // No LDS, no atomics: every output element has one writer and is a function of the input alone.  The kernels do not
 // check indices or finiteness: that is the caller's duty (kernels.py validates before launching).
 #include "common.hpp"
+#include "mesh_grid_host.hpp"
 #include "mesh_distance_core.hpp"
 
 namespace {
 
 constexpr int NTHREADS = 256;
+using nerf_grid::aligned8;
+using nerf_grid::LIMIT;
+using nerf_grid::make_grid;
 
 __global__ __launch_bounds__(NTHREADS) void face_cell_counts_kernel(const float* __restrict__ verts,
                                                                     const int32_t* __restrict__ faces, int64_t F,
@@ -51,24 +55,6 @@ __global__ __launch_bounds__(NTHREADS) void nearest_faces_kernel(const float* __
     closest[3 * i + 1] = best.p[1];
     closest[3 * i + 2] = best.p[2];
   }
-}
-
-constexpr int64_t LIMIT = int64_t(1) << 31;
-
-bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
-
-// lo, cell, inv, dims as the header states them; false on a value outside the contract
-bool make_grid(const float* lo, float cell, float inv, const int32_t* dims, nerf_mm::Grid& g) {
-  if (!lo || !dims) return false;
-  if (!(cell > 0.0f) || !(inv > 0.0f) || !isfinite(cell) || !isfinite(inv)) return false;
-  for (int c = 0; c < 3; ++c) {
-    if (!isfinite(lo[c]) || dims[c] < 1 || dims[c] > nerf_mm::MAX_DIM) return false;
-    g.lo[c] = lo[c];
-    g.dims[c] = dims[c];
-  }
-  g.cell = cell;
-  g.inv = inv;
-  return true;
 }
 
 }  // namespace

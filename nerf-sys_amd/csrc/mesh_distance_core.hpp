@@ -1,5 +1,5 @@
 // Exact point-to-surface distance: the closest point of a triangle, the cell keys of a face and the
-// exact nearest-face search through the uniform grid of mesh_metrics_core.hpp, written once for the device and for a
+// exact nearest-face search through the uniform grid of mesh_grid_core.hpp, written once for the device and for a
 // host compiler so that every loop can be run and checked under a host sanitizer without a GPU.
 // Build with -ffp-contract=off: every fp64 operation below rounds on its own.
 //
@@ -15,44 +15,31 @@
 // repeated index, when nerf_mm::face_cross is exactly (0, 0, 0), or when the walk reaches the interior with
 // va + vb + vc <= 0: no division by zero and no NaN leaves this file for finite input.
 //
-// The grid and the search.  A face is registered in every cell of the index box [cell_index(min corner),
-// cell_index(max corner)] of its bounding box (fminf / fmaxf over its three corners, per axis): key =
-// (cell_id << 32) | face.  Sorted ascending, the faces of a cell are contiguous and the cells of one (ix, iy) column are
-// contiguous in iz, exactly as for the point keys, so the search is nerf_mm::nearest with a face evaluation in place
-// of a point distance.  A face met in several cells is evaluated again: min is idempotent.  The search stops before
-// shell r >= 2 when nerf_mm::shell_can_stop holds for best_d2 rounded UP to fp32, that is when
+// The search.  The faces are registered in the grid of mesh_grid_core.hpp, key = (cell_id << 32) | face, in every cell
+// of the index box of their bounding box, so the search is that of nerf_mm::nearest (nerf_grid::walk_shells and
+// nerf_grid::for_run) with a face evaluation in place of a point distance.  A face met in several cells is evaluated
+// again: min is idempotent.  The search stops before shell r >= 2 when nerf_grid::shell_can_stop holds for best_d2
+// rounded UP to fp32.
 //
-//     best_d2 <= ((r - 1 - 2^-8) cell)^2 (1 - 2^-10).
-//
-// Why that is safe.  The grid's box holds every vertex (the caller builds it from the vertices' own minimum and
-// maximum).  Before shell r the cells of the cube of Chebyshev radius r - 1 around the query's clamped cell, clipped to
-// the grid, have all been searched.  A face that has not been evaluated is registered in none of them; its registered
-// cells form a box, the cube is a box, and two disjoint boxes of cells are separated along one axis: on that axis
-// every registered cell of the face differs from the query's cell by at least r.  The fp32 cell_index is monotone in
-// the coordinate (a difference, a product, a floor and a clamp, each monotone), and every real point of the face has
-// each coordinate between the smallest and the largest of its corners, so it computes a cell index between the two
-// ends of the face's index box: with the bound of mesh_metrics_core.hpp, |t - s| < delta = 2^-12 of a cell, every real
-// point of the face lies in its registered cells widened by delta.  The query lies in its own cell widened by delta,
-// or, when it was clamped, farther from every cell than a point of its border cell.  Hence the real distance from
-// the query to any point of an unevaluated face is at least (r - 1 - 2 delta) cell > (r - 1 - 2^-11) cell.  The d2
-// computed for such a face is the squared distance to a combination of its corners with weights in [0, 1] up to a
-// few roundings of 2^-53, so it is at least ((r - 1 - 2^-11) cell)^2 (1 - 2^-48); rounding best_d2 up to fp32 only
-// makes the test harder to pass.  The rule keeps 2^-8 - 2^-11 of a cell and 2^-10 relative in hand: when it fires,
-// every unevaluated face is strictly farther than the best, so neither the distance nor the smallest-index
-// tie-break can change.  The result is brute force's, bit for bit.  Tighten the slack only with an argument.
+// Why that is safe.  mesh_grid_core.hpp shows that before shell r the real distance from the query to any point of
+// an unevaluated face is at least (r - 1 - 2^-11) cell.  The part that is this search's own: the d2 computed for such
+// a face is the squared distance to a combination of its corners with weights in [0, 1] up to a few roundings of
+// 2^-53, so it is at least ((r - 1 - 2^-11) cell)^2 (1 - 2^-48); rounding best_d2 up to fp32 only makes the test
+// harder to pass.  The rule keeps 2^-8 - 2^-11 of a cell and 2^-10 relative in hand: when it fires, every unevaluated
+// face is strictly farther than the best, so neither the distance nor the smallest-index tie-break can change.  The
+// result is brute force's, bit for bit.  Tighten the slack only with an argument.
 #pragma once
 #include "mesh_metrics_core.hpp"
 
 namespace nerf_md {
 
-using nerf_mm::Grid;
+using nerf_grid::dot3;
+using nerf_grid::face_box;
+using nerf_grid::face_cell_count;
+using nerf_grid::face_keys;
+using nerf_grid::Grid;
 
 // ---------------------------------------------------------------- the closest point of a triangle
-
-NERF_MM_HD double dot3(const double a[3], const double b[3]) {
-  const double x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
-  return (x + y) + z;
-}
 
 // t >= 0 ? (t <= 1 ? t : 1) : 0: a NaN counts as 0
 NERF_MM_HD double clamp01(double t) { return t >= 0.0 ? (t <= 1.0 ? t : 1.0) : 0.0; }
@@ -156,11 +143,12 @@ NERF_MM_HD void segment(const double p0[3], const double p1[3], const double q[3
 // The squared distance from q to face f, in double, and the closest point rounded to fp32.
 NERF_MM_HD double closest_on_face(const float* p, const int32_t* faces, int64_t f, const float qf[3], float closest[3]) {
   const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  const nerf_grid::Corners t = nerf_grid::load_corners(p, faces, f);
   double a[3], b[3], c[3], q[3], r[3];
   for (int k = 0; k < 3; ++k) {
-    a[k] = (double)p[3 * i0 + k];
-    b[k] = (double)p[3 * i1 + k];
-    c[k] = (double)p[3 * i2 + k];
+    a[k] = (double)t.a[k];
+    b[k] = (double)t.b[k];
+    c[k] = (double)t.c[k];
     q[k] = (double)qf[k];
   }
   bool flat = i0 == i1 || i1 == i2 || i0 == i2;
@@ -182,36 +170,6 @@ NERF_MM_HD double closest_on_face(const float* p, const int32_t* faces, int64_t 
   return d2;
 }
 
-// ---------------------------------------------------------------- the cells of a face
-
-// the index box of face f: lo[c] <= hi[c] because cell_index is monotone
-NERF_MM_HD void face_box(const Grid& g, const float* p, const int32_t* faces, int64_t f, int32_t lo[3], int32_t hi[3]) {
-  const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-  for (int c = 0; c < 3; ++c) {
-    const float x0 = p[3 * i0 + c], x1 = p[3 * i1 + c], x2 = p[3 * i2 + c];
-    lo[c] = nerf_mm::cell_index(g, c, fminf(fminf(x0, x1), x2));
-    hi[c] = nerf_mm::cell_index(g, c, fmaxf(fmaxf(x0, x1), x2));
-  }
-}
-
-// the number of cells face f is registered in: at most 1024^3 = 2^30
-NERF_MM_HD int64_t face_cell_count(const Grid& g, const float* p, const int32_t* faces, int64_t f) {
-  int32_t lo[3], hi[3];
-  face_box(g, p, faces, f, lo, hi);
-  return ((int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1)) * (hi[2] - lo[2] + 1);
-}
-
-// the keys of face f, face_cell_count of them, in ascending cell_id order; every loop is bounded by a dim
-NERF_MM_HD void face_keys(const Grid& g, const float* p, const int32_t* faces, int64_t f, int64_t* out) {
-  int32_t lo[3], hi[3];
-  face_box(g, p, faces, f, lo, hi);
-  int64_t at = 0;
-  for (int32_t ix = lo[0]; ix <= hi[0]; ++ix)
-    for (int32_t iy = lo[1]; iy <= hi[1]; ++iy)
-      for (int32_t iz = lo[2]; iz <= hi[2]; ++iz)
-        out[at++] = (int64_t)(((uint64_t)nerf_mm::cell_id(g, ix, iy, iz) << 32) | (uint64_t)(uint32_t)f);
-}
-
 // ---------------------------------------------------------------- the search
 
 struct BestFace {
@@ -231,19 +189,6 @@ NERF_MM_HD void consider(const float* vertices, const int32_t* faces, int32_t f,
   }
 }
 
-// The faces registered in the cells (ix, iy, z0 .. z1) of one column: one lower bound, then a walk over the run (at
-// most n_keys keys).
-NERF_MM_HD void scan_run(const Grid& g, const float q[3], const int64_t* keys, int64_t n_keys, const float* vertices,
-                         const int32_t* faces, int32_t ix, int32_t iy, int32_t z0, int32_t z1, BestFace& best) {
-  const int64_t first = (int64_t)((uint64_t)nerf_mm::cell_id(g, ix, iy, z0) << 32);
-  const int64_t end = (int64_t)((uint64_t)(nerf_mm::cell_id(g, ix, iy, z1) + 1) << 32);
-  for (int64_t j = nerf_mm::lower_bound(keys, n_keys, first); j < n_keys; ++j) {
-    const int64_t key = keys[j];
-    if (key >= end) break;
-    consider(vertices, faces, (int32_t)(uint32_t)((uint64_t)key & 0xffffffffu), q, best);
-  }
-}
-
 // best_d2 rounded up to fp32 (+inf beyond the fp32 range), so that shell_can_stop errs towards searching on
 NERF_MM_HD float round_up(double d2) {
   float f = (float)d2;
@@ -251,35 +196,17 @@ NERF_MM_HD float round_up(double d2) {
   return f;
 }
 
-// The nearest face of q: the shells, columns and runs of nerf_mm::nearest.  n_keys == 0: d2 = +inf, face = -1, the
-// point = q.
+// The nearest face of q.  The walk of a run is bounded by n_keys.  n_keys == 0: d2 = +inf, face = -1, the point = q.
 NERF_MM_HD BestFace nearest_face(const Grid& g, const float q[3], const int64_t* keys, int64_t n_keys,
                                  const float* vertices, const int32_t* faces) {
   BestFace best = {(double)INFINITY, -1, {q[0], q[1], q[2]}};
   if (n_keys <= 0) return best;
-  const int32_t nx = g.dims[0], ny = g.dims[1], nz = g.dims[2];
-  const int32_t cx = nerf_mm::cell_index(g, 0, q[0]), cy = nerf_mm::cell_index(g, 1, q[1]),
-                cz = nerf_mm::cell_index(g, 2, q[2]);
-  const int32_t shells = nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz);
-  for (int32_t r = 0; r < shells; ++r) {
-    if (r >= 2 && nerf_mm::shell_can_stop(round_up(best.d2), r, g.cell)) break;
-    if (cx - r < 0 && cx + r > nx - 1 && cy - r < 0 && cy + r > ny - 1 && cz - r < 0 && cz + r > nz - 1)
-      break;  // this shell and every later one lie outside the grid: every cell has been searched
-    const int32_t x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < nx - 1 ? cx + r : nx - 1;
-    const int32_t y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < ny - 1 ? cy + r : ny - 1;
-    const int32_t z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < nz - 1 ? cz + r : nz - 1;
-    for (int32_t ix = x0; ix <= x1; ++ix) {
-      const bool rim_x = ix == cx - r || ix == cx + r;
-      for (int32_t iy = y0; iy <= y1; ++iy) {
-        if (rim_x || iy == cy - r || iy == cy + r) {
-          scan_run(g, q, keys, n_keys, vertices, faces, ix, iy, z0, z1, best);
-        } else {
-          if (cz - r >= 0) scan_run(g, q, keys, n_keys, vertices, faces, ix, iy, cz - r, cz - r, best);
-          if (cz + r <= nz - 1) scan_run(g, q, keys, n_keys, vertices, faces, ix, iy, cz + r, cz + r, best);
-        }
-      }
-    }
-  }
+  nerf_grid::walk_shells(
+      g, q, [&](int32_t r) { return nerf_grid::shell_can_stop(round_up(best.d2), r, g.cell); },
+      [&](int32_t ix, int32_t iy, int32_t z0, int32_t z1) {
+        nerf_grid::for_run(g, keys, n_keys, ix, iy, z0, z1,
+                           [&](int64_t, int64_t, int32_t f) { consider(vertices, faces, f, q, best); });
+      });
   return best;
 }
 

@@ -1,5 +1,5 @@
 // Point-in-mesh by exact crossing counts: the faces crossed by the vertical ray q + t e_z, t > 0, from
-// a query q, found through the face grid of mesh_distance_core.hpp, written once for the device and for a host
+// a query q, found through the face grid of mesh_grid_core.hpp, written once for the device and for a host
 // compiler so that every loop can be run and checked under a host sanitizer without a GPU.
 // Build with -ffp-contract=off: every fp64 operation below rounds on its own (two_sum depends on it).
 //
@@ -44,10 +44,10 @@
 // two_sum's error term is exact throughout.  The expansion lives in six named doubles, no indexed array (§3.11.6
 // records what indexing by a run-time value did to ray_cast_kernel).
 //
-// The walk.  (cx, cy, cz) = cell_index of q per axis.  One nerf_mm::lower_bound at cell_id(cx, cy, cz) << 32, then the
-// keys up to the end of the column (cx, cy): the ray runs along z because a column's cells are contiguous in the
-// sorted keys.  A face registered in several cells of the column is tested at one key only: the one whose
-// iz == max(cell_index(min corner z), cz).
+// The walk.  (cx, cy, cz) = cell_index of q per axis.  nerf_grid::for_run over the cells (cx, cy, cz .. nz - 1): one
+// lower bound at cell_id(cx, cy, cz) << 32, then the keys up to the end of the column (cx, cy): the ray runs along z
+// because a column's cells are contiguous in the sorted keys.  A face registered in several cells of the column is
+// tested at one key only: the one whose iz == max(cell_index(min corner z), cz).
 // Why this finds every crossed face exactly once.  cell_index is monotone in the coordinate (a difference, a
 // product, a floor and a clamp, each monotone).  For a crossed face rule 1 gives min x <= qx <= max x, hence
 // cell_index(min x) <= cx <= cell_index(max x), and the same in y: the face is registered in the column (cx, cy), in
@@ -62,7 +62,9 @@
 
 namespace nerf_mi {
 
-using nerf_mm::Grid;
+using nerf_grid::Corners;
+using nerf_grid::Grid;
+using nerf_grid::load_corners;
 
 constexpr uint64_t BOX_STREAM = 0x626f78ULL;  // "box": the streams of a box point are BOX_STREAM + 0, 1, 2
 constexpr double FILTER = 0x1p-48;
@@ -153,29 +155,9 @@ NERF_MM_HD int crossed_corners(const float a[3], const float b[3], const float c
     e2[k] = (double)c[k] - o;
     w[k] = (double)q[k] - o;
   }
-  const double x0 = e1[1] * e2[2], x1 = e1[2] * e2[1];
-  const double y0 = e1[2] * e2[0], y1 = e1[0] * e2[2];
-  const double z0 = e1[0] * e2[1], z1 = e1[1] * e2[0];
-  n[0] = x0 - x1;
-  n[1] = y0 - y1;
-  n[2] = z0 - z1;
-  const double g = nerf_md::dot3(n, w);
+  nerf_grid::cross3(e1, e2, n);
+  const double g = nerf_grid::dot3(n, w);
   return ((g < 0.0 && s > 0) || (g > 0.0 && s < 0)) ? s : 0;
-}
-
-struct Corners {
-  float a[3], b[3], c[3];
-};
-
-NERF_MM_HD Corners load_corners(const float* verts, const int32_t* faces, int64_t f) {
-  const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-  Corners t;
-  for (int k = 0; k < 3; ++k) {
-    t.a[k] = verts[3 * i0 + k];
-    t.b[k] = verts[3 * i1 + k];
-    t.c[k] = verts[3 * i2 + k];
-  }
-  return t;
 }
 
 struct Count {
@@ -204,25 +186,20 @@ NERF_MM_HD Count count_crossings(const Grid& g, const float q[3], const int64_t*
   Count n = {0, 0};
   if (counts) counts[0] = counts[1] = counts[2] = 0;
   if (n_keys <= 0) return n;
-  const int32_t cx = nerf_mm::cell_index(g, 0, q[0]), cy = nerf_mm::cell_index(g, 1, q[1]),
-                cz = nerf_mm::cell_index(g, 2, q[2]);
-  const int64_t base = nerf_mm::cell_id(g, cx, cy, 0);
-  const int64_t first = (int64_t)((uint64_t)(base + cz) << 32);
-  const int64_t end = (int64_t)((uint64_t)(base + g.dims[2]) << 32);
-  for (int64_t j = nerf_mm::lower_bound(keys, n_keys, first); j < n_keys; ++j) {
-    const int64_t key = keys[j];
-    if (key >= end) break;
+  const int32_t cx = nerf_grid::cell_index(g, 0, q[0]), cy = nerf_grid::cell_index(g, 1, q[1]),
+                cz = nerf_grid::cell_index(g, 2, q[2]);
+  const int64_t base = nerf_grid::cell_id(g, cx, cy, 0);
+  nerf_grid::for_run(g, keys, n_keys, cx, cy, cz, g.dims[2] - 1, [&](int64_t, int64_t cell, int32_t f) {
     if (counts) ++counts[0];
-    const int64_t f = (int64_t)((uint64_t)key & 0xffffffffu);
-    const int32_t iz = (int32_t)((key >> 32) - base);
-    const Corners t = load_corners(verts, faces, f);
-    const int32_t lz = nerf_mm::cell_index(g, 2, fminf(fminf(t.a[2], t.b[2]), t.c[2]));
-    if (iz != (lz > cz ? lz : cz)) continue;
+    const int32_t iz = (int32_t)(cell - base);
+    const Corners t = load_corners(verts, faces, (int64_t)(uint32_t)f);
+    const int32_t lz = nerf_grid::cell_index(g, 2, fminf(fminf(t.a[2], t.b[2]), t.c[2]));
+    if (iz != (lz > cz ? lz : cz)) return;
     if (counts) ++counts[1];
     const int s = crossed_corners(t.a, t.b, t.c, q, counts ? counts + 2 : nullptr);
     n.crossings += s != 0;
     n.winding += s;
-  }
+  });
   return n;
 }
 

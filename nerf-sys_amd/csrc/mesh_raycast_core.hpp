@@ -1,5 +1,5 @@
 // Nearest-hit ray casting against a mesh: the ray / triangle test and the walk of a ray through the
-// face grid of mesh_distance_core.hpp, written once for the device and for a host compiler so that every loop can be
+// face grid of mesh_grid_core.hpp, written once for the device and for a host compiler so that every loop can be
 // run and checked under a host sanitizer without a GPU.
 // Build with -ffp-contract=off: every fp64 operation below rounds on its own.
 //
@@ -23,14 +23,14 @@
 // first on a tie.  The layers i of cells along M are walked in the ray's direction from the layer of c_M(t0), one
 // back.  Layer i, widened by S on both sides, is crossed between tin and tout, (plane - rel_M) / d_M for its two
 // planes; over [max(tin, t0), min(tout, t1)] the two other coordinates run between their values at the two ends, and
-// the cells floor(min - S) .. floor(max + S), clamped to the grid, are searched: one nerf_mm::lower_bound per run
+// the cells floor(min - S) .. floor(max + S), clamped to the grid, are searched: one nerf_grid::lower_bound per run
 // of cells contiguous in z, every face of a run tested (a face met again changes nothing: the comparison is strict).
 // The minor slopes are at most 1, a widened layer is 1 + 2 S thick, so that is at most 3 x 3 cells.  The walk stops
 // before a layer with tin > best t, or tin > t1.  Every loop is bounded by a dim or by n_keys.
 //
 // Why the walk misses nothing.  Take a hit (t, f) that the test accepts.
 // (1) P_k(t) lies in the box of f widened by m on every axis.  The caller refuses a grid with m > 2^-10 cell (that is
-//     cell < 2^-20 of the largest |coordinate|: sixteen fp32 ulps, no real restriction).  By mesh_distance_core.hpp
+//     cell < 2^-20 of the largest |coordinate|: sixteen fp32 ulps, no real restriction).  By mesh_grid_core.hpp
 //     every real point of f's box lies in its registered cells widened by delta = 2^-12, so P(t) lies in the
 //     registered cells of f widened by delta + 2^-10: there is a registered cell (jx, jy, jz) with
 //     j_k - delta - 2^-10 <= (P_k - lo_k) / cell <= j_k + 1 + delta + 2^-10 on every axis.
@@ -59,7 +59,8 @@
 
 namespace nerf_mr {
 
-using nerf_mm::Grid;
+using nerf_grid::cross3;
+using nerf_grid::Grid;
 
 constexpr double SLACK = 0.015625;           // S = 2^-6 of a cell
 constexpr double FAR_ORIGIN = 4294967296.0;  // 2^32 cells: beyond it every face is tested
@@ -87,15 +88,6 @@ NERF_MM_HD Ray load_ray(const float* rays, int64_t i) {
 
 // ---------------------------------------------------------------- the hit test
 
-NERF_MM_HD void cross3(const double a[3], const double b[3], double c[3]) {
-  const double x0 = a[1] * b[2], x1 = a[2] * b[1];
-  const double y0 = a[2] * b[0], y1 = a[0] * b[2];
-  const double z0 = a[0] * b[1], z1 = a[1] * b[0];
-  c[0] = x0 - x1;
-  c[1] = y0 - y1;
-  c[2] = z0 - z1;
-}
-
 // The rule of the header comment for face f: true and (t, u, v) on a hit.
 NERF_MM_HD bool hit_face(const float* verts, const int32_t* faces, int64_t f, const Ray& r, double margin, bool cull,
                          double& t, double& u, double& v) {
@@ -104,26 +96,27 @@ NERF_MM_HD bool hit_face(const float* verts, const int32_t* faces, int64_t f, co
   double x[3];
   nerf_mm::face_cross(verts, faces, f, x);
   if (x[0] == 0.0 && x[1] == 0.0 && x[2] == 0.0) return false;
+  const nerf_grid::Corners c = nerf_grid::load_corners(verts, faces, f);
   double a[3], e1[3], e2[3], s[3], p[3], q[3];
   for (int k = 0; k < 3; ++k) {
-    a[k] = (double)verts[3 * i0 + k];
-    e1[k] = (double)verts[3 * i1 + k] - a[k];
-    e2[k] = (double)verts[3 * i2 + k] - a[k];
+    a[k] = (double)c.a[k];
+    e1[k] = (double)c.b[k] - a[k];
+    e2[k] = (double)c.c[k] - a[k];
     s[k] = r.o[k] - a[k];
   }
   cross3(r.d, e2, p);
-  const double det = nerf_md::dot3(e1, p);
+  const double det = nerf_grid::dot3(e1, p);
   if (det == 0.0) return false;
   if (cull && det <= 0.0) return false;
-  u = nerf_md::dot3(s, p) / det;
+  u = nerf_grid::dot3(s, p) / det;
   cross3(s, e1, q);
-  v = nerf_md::dot3(r.d, q) / det;
-  t = nerf_md::dot3(e2, q) / det;
+  v = nerf_grid::dot3(r.d, q) / det;
+  t = nerf_grid::dot3(e2, q) / det;
   if (!(u >= 0.0 && u <= 1.0 && v >= 0.0 && u + v <= 1.0)) return false;
   if (!(r.near <= t && t <= r.far)) return false;
   for (int k = 0; k < 3; ++k) {
-    const float c0 = verts[3 * i0 + k], c1 = verts[3 * i1 + k], c2 = verts[3 * i2 + k];
-    const double mn = (double)fminf(fminf(c0, c1), c2) - margin, mx = (double)fmaxf(fmaxf(c0, c1), c2) + margin;
+    const double mn = (double)fminf(fminf(c.a[k], c.b[k]), c.c[k]) - margin,
+                 mx = (double)fmaxf(fmaxf(c.a[k], c.b[k]), c.c[k]) + margin;
     const double td = t * r.d[k];
     const double P = r.o[k] + td;
     if (!(P >= mn && P <= mx)) return false;
@@ -158,23 +151,6 @@ NERF_MM_HD Hit brute(const Ray& r, const float* verts, const int32_t* faces, int
 
 // ---------------------------------------------------------------- the walk
 
-// The faces registered in the cells (ix, iy, z0 .. z1) of one column: one lower bound, then a walk over the run (at
-// most n_keys keys).  Returns the number of faces tested (the host tools report it; the kernel drops it).
-NERF_MM_HD int64_t scan_run(const Grid& g, const Ray& r, const int64_t* keys, int64_t n_keys, const float* verts,
-                            const int32_t* faces, int32_t ix, int32_t iy, int32_t z0, int32_t z1, double margin,
-                            bool cull, Hit& best) {
-  const int64_t first = (int64_t)((uint64_t)nerf_mm::cell_id(g, ix, iy, z0) << 32);
-  const int64_t end = (int64_t)((uint64_t)(nerf_mm::cell_id(g, ix, iy, z1) + 1) << 32);
-  int64_t tested = 0;
-  for (int64_t j = nerf_mm::lower_bound(keys, n_keys, first); j < n_keys; ++j) {
-    const int64_t key = keys[j];
-    if (key >= end) break;
-    consider(verts, faces, (int32_t)(uint32_t)((uint64_t)key & 0xffffffffu), r, margin, cull, best);
-    ++tested;
-  }
-  return tested;
-}
-
 // floor(x) clamped to [0, dim - 1] as a double, then converted: a NaN counts as 0
 NERF_MM_HD int32_t floor_cell(double x, int32_t dim) {
   const double f = floor(x), top = (double)(dim - 1);
@@ -193,7 +169,8 @@ NERF_MM_HD bool minor_cells(double rel, double d, int32_t dim, double a, double 
   return ph >= 0.0 && pl <= (double)dim;
 }
 
-// The nearest hit of ray r.  n_keys == 0: a miss.  counts, when given, receives {layers walked, faces tested}.
+// The nearest hit of ray r.  n_keys == 0: a miss.  counts, when given, receives {layers walked, faces tested} (the
+// host tools report them; the kernel drops them).
 NERF_MM_HD Hit cast(const Grid& g, const Ray& r, const int64_t* keys, int64_t n_keys, const float* verts,
                     const int32_t* faces, int64_t F, double margin, bool cull, int64_t* counts = nullptr) {
   Hit best = miss();
@@ -252,7 +229,10 @@ NERF_MM_HD Hit cast(const Grid& g, const Ray& r, const int64_t* keys, int64_t n_
     if (!inside) continue;
     for (int32_t ix = x0; ix <= x1; ++ix)
       for (int32_t iy = y0; iy <= y1; ++iy)
-        tested += scan_run(g, r, keys, n_keys, verts, faces, ix, iy, z0, z1, margin, cull, best);
+        nerf_grid::for_run(g, keys, n_keys, ix, iy, z0, z1, [&](int64_t, int64_t, int32_t f) {
+          consider(verts, faces, f, r, margin, cull, best);
+          ++tested;
+        });
   }
   if (counts) counts[0] = layers, counts[1] = tested;
   return best;

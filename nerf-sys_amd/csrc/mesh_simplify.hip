@@ -19,6 +19,7 @@
 //
 // The kernels do not check indices or finiteness: that is the caller's duty (kernels.py validates before launching).
 #include "common.hpp"
+#include "mesh_grid_host.hpp"
 #include "mesh_simplify_core.hpp"
 
 namespace {
@@ -128,8 +129,7 @@ __global__ __launch_bounds__(NTHREADS) void reduce_finalize_kernel(const float* 
   const int32_t n = rep ? count[v] : 1;  // a representative counts itself: n >= 1
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    float t;
-    const int32_t i = nerf_hs::cell_index(g, c, verts[3 * v + c], t);
+    const int32_t i = nerf_hs::cell_index(g, c, verts[3 * v + c]);
     out_v[3 * v + c] = rep ? nerf_hs::mean_pos(g, c, i, row[c], n) : 0.0f;
   }
   int w = 3;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(NTHREADS) void faces_lookup_kernel(const int32_t* _
   report(status, ok, probes, 2);
 }
 
-bool sizes_ok(int64_t F, int64_t V) { return F >= 0 && V >= 0 && V < (int64_t(1) << 31) && 3 * F < (int64_t(1) << 31); }
+bool sizes_ok(int64_t F, int64_t V) { return F >= 0 && V >= 0 && V < nerf_grid::LIMIT && 3 * F < nerf_grid::LIMIT; }
 
 bool table_ok(int64_t items, int table_log2) {
   return table_log2 >= 0 && table_log2 <= 31 && (int64_t(1) << table_log2) > items;
@@ -221,14 +221,6 @@ bool grid_ok(const float* lo, float cell, float inv, const int32_t* dims) {
   for (int c = 0; c < 3; ++c)
     if (dims[c] < 1 || dims[c] > (1 << 20)) return false;
   return true;
-}
-
-Grid make_grid(const float* lo, float cell, float inv, const int32_t* dims) {
-  Grid g;
-  for (int c = 0; c < 3; ++c) g.lo[c] = lo[c], g.dims[c] = dims[c];
-  g.cell = cell;
-  g.inv = inv;
-  return g;
 }
 
 int reduce_words(int has_normals, int has_colors) { return 3 * (1 + (has_normals ? 1 : 0) + (has_colors ? 1 : 0)); }
@@ -255,7 +247,7 @@ extern "C" int nerf_mesh_cluster_labels(const float* vertices, int64_t V, const 
   const int64_t slots = int64_t(1) << table_log2;
   e = hipMemsetAsync(table, 0xff, 4 * slots, stream);  // EMPTY = -1
   if (e != hipSuccess) return nerf_hip_status(e);
-  const Grid g = make_grid(lo, cell, inv, dims);
+  const Grid g = nerf_grid::fill_grid(lo, cell, inv, dims);
   const unsigned vb = (unsigned)nerf_cdiv(V, NTHREADS);
   const uint32_t mask = (uint32_t)(slots - 1);
   cluster_keys_kernel<<<vb, NTHREADS, 0, stream>>>(vertices, V, g, keys);
@@ -284,7 +276,7 @@ extern "C" int nerf_mesh_cluster_reduce(const float* vertices, const int32_t* la
   const int words = reduce_words(has_n, has_c);
   unsigned long long* acc = (unsigned long long*)workspace;
   int32_t* count = (int32_t*)((char*)workspace + round16(8 * V * words));
-  const Grid g = make_grid(lo, cell, inv, dims);
+  const Grid g = nerf_grid::fill_grid(lo, cell, inv, dims);
   const unsigned vb = (unsigned)nerf_cdiv(V, NTHREADS);
   reduce_init_kernel<<<(unsigned)nerf_cdiv(V * words, NTHREADS), NTHREADS, 0, stream>>>(acc, V * words, count, V);
   reduce_accumulate_kernel<<<vb, NTHREADS, 0, stream>>>(vertices, labels, normals, colors, V, g, words, acc, count);

@@ -10,16 +10,15 @@
 // advances past a slot only after it has read a value of another key there, and never past an empty one.  Every
 // access during the insert is a relaxed agent-scope atomic; the lookup runs in a later launch.
 #pragma once
-#include <math.h>
-#include <stdint.h>
+#include "mesh_grid_core.hpp"
 
-#if defined(__HIPCC__)
-#define NERF_HS_HD __host__ __device__ __forceinline__
-#else
-#define NERF_HS_HD inline
-#endif
+#define NERF_HS_HD NERF_GRID_HD
 
 namespace nerf_hs {
+
+using nerf_grid::cell_index;
+using nerf_grid::clampf;
+using nerf_grid::Grid;
 
 constexpr int32_t EMPTY = -1;
 
@@ -103,32 +102,15 @@ NERF_HS_HD int32_t lookup(const int32_t* table, uint32_t mask, uint64_t h, int32
 // ---------------------------------------------------------------- the contract's arithmetic (build with
 // -ffp-contract=off: every fp32 and fp64 operation below rounds on its own)
 
-// x >= a ? (x <= b ? x : b) : a: a NaN counts as the lower bound
-NERF_HS_HD float clampf(float x, float a, float b) { return x >= a ? (x <= b ? x : b) : a; }
-
-struct Grid {
-  float lo[3];
-  float cell, inv;
-  int32_t dims[3];
-};
-
-// the cell index of coordinate x on axis c (clamped as a float, then converted) and t = (x - lo) * inv
-NERF_HS_HD int32_t cell_index(const Grid& g, int c, float x, float& t) {
-  t = (x - g.lo[c]) * g.inv;
-  return (int32_t)clampf(floorf(t), 0.0f, (float)(g.dims[c] - 1));
-}
-
+// the cell key of vertex v: nerf_grid::cell_id of its three cell indices (dims up to 2^20 here, so up to 2^60)
 NERF_HS_HD int64_t cell_key(const Grid& g, const float* v) {
-  float t;
-  const int64_t ix = cell_index(g, 0, v[0], t), iy = cell_index(g, 1, v[1], t), iz = cell_index(g, 2, v[2], t);
-  return (ix * g.dims[1] + iy) * g.dims[2] + iz;
+  return nerf_grid::cell_id(g, cell_index(g, 0, v[0]), cell_index(g, 1, v[1]), cell_index(g, 2, v[2]));
 }
 
 // the position inside the cell in 24-bit fixed point, 0 .. 2^24
 NERF_HS_HD uint32_t quant_pos(const Grid& g, int c, float x) {
-  float t;
-  const int32_t i = cell_index(g, c, x, t);
-  return (uint32_t)(clampf(t - (float)i, 0.0f, 1.0f) * 16777216.0f);
+  const float t = nerf_grid::cell_coord(g, c, x);
+  return (uint32_t)(clampf(t - (float)cell_index(g, c, x), 0.0f, 1.0f) * 16777216.0f);
 }
 
 NERF_HS_HD int64_t quant_normal(float n) { return (int64_t)rintf(clampf(n, -1.0f, 1.0f) * 1048576.0f); }

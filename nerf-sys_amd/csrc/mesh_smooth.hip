@@ -14,6 +14,7 @@
 // No atomics at all: every output element has one writer, or (the boundary flags) several writers of the same value.
 // The kernels do not check indices or finiteness: that is the caller's duty (kernels.py validates before launching).
 #include "common.hpp"
+#include "mesh_grid_host.hpp"
 #include "mesh_smooth_core.hpp"
 
 namespace {
@@ -69,9 +70,8 @@ __global__ __launch_bounds__(NTHREADS) void vertex_normals_kernel(const float* _
   nerf_ms::vertex_normal(verts, faces, row_off, col, v, out);
 }
 
-constexpr int64_t LIMIT = int64_t(1) << 31;
-
-bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
+using nerf_grid::aligned8;
+using nerf_grid::LIMIT;
 
 }  // namespace
 

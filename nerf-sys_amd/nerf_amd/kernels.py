@@ -929,45 +929,63 @@ def _sorted_cell_keys(points, m, lo_c, inv, dims_c):
     return keys, (keys & 0xffffffff).to(torch.int32)
 
 
-def points_grid(points, cell_size=None):
-    """The search grid of a reference point set (nerf_points_cell_keys -> torch.sort -> nerf_gather_rows): points
-    (m,3) float32, finite.  Returns the dict {keys (m,) int64 sorted, points (m,3) float32 in key order, lo (3 floats),
-    cell, inv (fp32 values as floats), dims (3 ints), m}.  lo is the minimum of the points.  The default cell is
-    longest extent / clamp(ceil(sqrt(m) / 2), 1, 1024), a handful of surface samples per occupied cell; an all-zero
-    extent gets cell = 1.  dims = floor((max - lo) * inv) + 1 per axis in fp32 (1 for an axis of zero extent).
-    ``cell_size``: a finite positive float; ValueError if it needs more than 1024 cells on an axis (the cap keeps the
-    fp32 cell index within 2^-12 of a cell, which the search's stopping rule rests on).  Memory: 8 + 12 bytes per
-    point beyond the input, no cell table.  One host read: the box (it carries the finiteness check)."""
-    import math
+def _run_sorted(query, n, grid_c, outs, run):
+    """run(q, *outs) with the queries in the order of their own cell keys (one key launch, a sort, a gather), every
+    output scattered back to the caller's order; ``outs`` may hold None for an output that is not wanted."""
+    lo_c, _, inv, dims_c = grid_c
+    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
+    sorted_outs = [None if o is None else torch.empty_like(o) for o in outs]
+    run(_gather3(query, order), *sorted_outs)
+    order = order.to(torch.int64)
+    for o, so in zip(outs, sorted_outs):
+        if o is not None:
+            o[order] = so
 
+
+def _cell_size_arg(cell_size):
+    """(cell, inv) as fp32 numpy values: ValueError unless cell_size is a finite positive float32 with a finite
+    reciprocal."""
     import numpy as np
-    m = _points_arg(points, "points")
-    if cell_size is not None:
-        with np.errstate(all="ignore"):
-            try:
-                cell = np.float32(cell_size)
-            except (TypeError, ValueError):
-                raise ValueError(f"cell_size must be a float, got {cell_size!r}") from None
-            inv = np.float32(1.0) / cell
-        if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
-            raise ValueError(f"cell_size must be a finite positive float32 with a finite reciprocal, got {cell_size!r}")
-    dev = points.device
-    if m == 0:
-        cell = np.float32(1.0) if cell_size is None else cell
-        return {"keys": torch.empty(0, dtype=torch.int64, device=dev), "points": points.new_empty((0, 3)),
-                "lo": [0.0, 0.0, 0.0], "cell": float(cell), "inv": float(np.float32(1.0) / cell), "dims": [1, 1, 1],
-                "m": 0}
+    with np.errstate(all="ignore"):
+        try:
+            cell = np.float32(cell_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"cell_size must be a float, got {cell_size!r}") from None
+        inv = np.float32(1.0) / cell
+    if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
+        raise ValueError(f"cell_size must be a finite positive float32 with a finite reciprocal, got {cell_size!r}")
+    return cell, inv
+
+
+def _finite_box(points, what):
+    """The per-axis minimum and maximum of points (n,3), n > 0, as 6 fp32 numpy values (one host read); ValueError
+    unless they are finite."""
+    import numpy as np
     mm = [torch.aminmax(points[:, c]) for c in range(3)]
     box = np.asarray(torch.stack([x.min for x in mm] + [x.max for x in mm]).tolist(), np.float32)
     if not np.isfinite(box).all():
-        raise ValueError("points must be finite")
+        raise ValueError(f"{what} must be finite")
+    return box
+
+
+def _grid_from_box(box, count, cell_size, what):
+    """The grid (lo, cell, inv, dims) of ``count`` items in ``box`` (of _finite_box; None for no items: one cell at the
+    origin): lo 3 floats, cell and inv fp32 values as floats, dims 3 ints.  ``cell_size`` None: the default cell,
+    longest extent / clamp(ceil(sqrt(count) / 2), 1, 1024), 1 for an all-zero extent; otherwise the caller has passed
+    it through _cell_size_arg already."""
+    import math
+
+    import numpy as np
+    cell, inv = (np.float32(1.0), np.float32(1.0)) if cell_size is None else _cell_size_arg(cell_size)
+    if box is None:
+        return [0.0, 0.0, 0.0], float(cell), float(inv), [1, 1, 1]
     lo = box[:3]
     with np.errstate(all="ignore"):
         ext = box[3:] - lo
         if not np.isfinite(ext).all():
-            raise ValueError("the extent of the points overflows float32")
+            raise ValueError(f"the extent of the {what} overflows float32")
         if cell_size is None:
-            k = min(max(math.ceil(math.sqrt(m) / 2.0), 1), MAX_GRID_DIM)
+            k = min(max(math.ceil(math.sqrt(count) / 2.0), 1), MAX_GRID_DIM)
             cell = ext.max() / np.float32(k) if ext.max() > 0 else np.float32(1.0)
             inv = np.float32(1.0) / cell
             if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
@@ -977,11 +995,36 @@ def points_grid(points, cell_size=None):
         cells = np.minimum(cells, MAX_GRID_DIM - 1)  # only rounding can exceed it; the kernel clamps into the last cell
     elif not np.isfinite(cells).all() or cells.max() + 1 > MAX_GRID_DIM:
         raise ValueError(f"cell_size {cell_size!r} needs more than {MAX_GRID_DIM} cells along an axis")
-    dims = [int(c) + 1 for c in cells]
-    lo_c, dims_c = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int32 * 3)(*dims)
-    keys, order = _sorted_cell_keys(points, m, lo_c, float(inv), dims_c)
-    return {"keys": keys, "points": _gather3(points, order), "lo": lo.tolist(), "cell": float(cell),
-            "inv": float(inv), "dims": dims, "m": m}
+    return lo.tolist(), float(cell), float(inv), [int(c) + 1 for c in cells]
+
+
+def _grid_c(grid):
+    """The ctypes arguments (lo, cell, inv, dims) of a grid dict."""
+    return ((ctypes.c_float * 3)(*grid["lo"]), float(grid["cell"]), float(grid["inv"]),
+            (ctypes.c_int32 * 3)(*grid["dims"]))
+
+
+def points_grid(points, cell_size=None):
+    """The search grid of a reference point set (nerf_points_cell_keys -> torch.sort -> nerf_gather_rows): points
+    (m,3) float32, finite.  Returns the dict {keys (m,) int64 sorted, points (m,3) float32 in key order, lo (3 floats),
+    cell, inv (fp32 values as floats), dims (3 ints), m}.  lo is the minimum of the points.  The default cell is
+    longest extent / clamp(ceil(sqrt(m) / 2), 1, 1024), a handful of surface samples per occupied cell; an all-zero
+    extent gets cell = 1.  dims = floor((max - lo) * inv) + 1 per axis in fp32 (1 for an axis of zero extent).
+    ``cell_size``: a finite positive float; ValueError if it needs more than 1024 cells on an axis (the cap keeps the
+    fp32 cell index within 2^-12 of a cell, which the search's stopping rule rests on).  Memory: 8 + 12 bytes per
+    point beyond the input, no cell table.  One host read: the box (it carries the finiteness check)."""
+    m = _points_arg(points, "points")
+    if cell_size is not None:
+        _cell_size_arg(cell_size)
+    lo, cell, inv, dims = _grid_from_box(_finite_box(points, "points") if m else None, m, cell_size, "points")
+    grid = {"lo": lo, "cell": cell, "inv": inv, "dims": dims, "m": m}
+    if m:
+        lo_c, _, _, dims_c = _grid_c(grid)
+        grid["keys"], order = _sorted_cell_keys(points, m, lo_c, inv, dims_c)
+        grid["points"] = _gather3(points, order)
+    else:
+        grid["keys"], grid["points"] = torch.empty(0, dtype=torch.int64, device=points.device), points.new_empty((0, 3))
+    return grid
 
 
 def _finite_points(points, name):
@@ -1008,43 +1051,21 @@ def points_nearest(query, grid, sort_queries=True, finite_checked=False):
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     if n == 0:
         return d2, idx
-    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
-    cell, inv = float(grid["cell"]), float(grid["inv"])
+    grid_c = _grid_c(grid)
     L = lib()
 
     def run(q, out_d2, out_idx):
         check(L.nerf_points_nearest(ptr(q), n, ptr(grid["keys"]) if m else None, ptr(grid["points"]) if m else None,
-                                    m, lo_c, cell, inv, dims_c, ptr(out_d2), ptr(out_idx), stream()),
-              "nerf_points_nearest")
+                                    m, *grid_c, ptr(out_d2), ptr(out_idx), stream()), "nerf_points_nearest")
 
     if not sort_queries or m == 0:
         run(query, d2, idx)
-        return d2, idx
-    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
-    sd2, sidx = torch.empty_like(d2), torch.empty_like(idx)
-    run(_gather3(query, order), sd2, sidx)
-    order = order.to(torch.int64)
-    d2[order] = sd2
-    idx[order] = sidx
+    else:
+        _run_sorted(query, n, grid_c, (d2, idx), run)
     return d2, idx
 
 
 # ------------------------------------------------------------------ exact point-to-surface distance
-
-
-def _cell_size_arg(cell_size):
-    """(cell, inv) as fp32 numpy values: ValueError unless cell_size is a finite positive float32 with a finite
-    reciprocal (the rule of points_grid)."""
-    import numpy as np
-    with np.errstate(all="ignore"):
-        try:
-            cell = np.float32(cell_size)
-        except (TypeError, ValueError):
-            raise ValueError(f"cell_size must be a float, got {cell_size!r}") from None
-        inv = np.float32(1.0) / cell
-    if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
-        raise ValueError(f"cell_size must be a finite positive float32 with a finite reciprocal, got {cell_size!r}")
-    return cell, inv
 
 
 _FACE_GRID_KEYS = {"keys", "lo", "cell", "inv", "dims", "n_keys", "F"}
@@ -1062,54 +1083,45 @@ def mesh_face_grid(vertices, faces, cell_size=None):
     ValueError before the key launch when the faces have 2^31 keys or more between them (a finer cell_size, or faces
     that span the grid, multiply the keys: 8 bytes each).  F == 0 gives an empty grid.  Host reads: the box (it carries
     the finiteness check), the index range, the total number of keys."""
-    import math
-
-    import numpy as np
     V = _vertices_arg(vertices)
     _, F = _faces_arg(faces, V)
     if cell_size is not None:
-        cell, inv = _cell_size_arg(cell_size)
+        _cell_size_arg(cell_size)
     dev = vertices.device
-    if V:
-        mm = [torch.aminmax(vertices[:, c]) for c in range(3)]
-        box = np.asarray(torch.stack([x.min for x in mm] + [x.max for x in mm]).tolist(), np.float32)
-        if not np.isfinite(box).all():
-            raise ValueError("vertices must be finite")
+    box = _finite_box(vertices, "vertices") if V else None
+    lo, cell, inv, dims = _grid_from_box(box if F else None, F, cell_size, "vertices")
+    grid = {"lo": lo, "cell": cell, "inv": inv, "dims": dims, "n_keys": 0, "F": F}
     if F == 0:
-        cell = np.float32(1.0) if cell_size is None else cell
-        return {"keys": torch.empty(0, dtype=torch.int64, device=dev), "lo": [0.0, 0.0, 0.0], "cell": float(cell),
-                "inv": float(np.float32(1.0) / cell), "dims": [1, 1, 1], "n_keys": 0, "F": 0}
-    lo = box[:3]
-    with np.errstate(all="ignore"):
-        ext = box[3:] - lo
-        if not np.isfinite(ext).all():
-            raise ValueError("the extent of the vertices overflows float32")
-        if cell_size is None:
-            k = min(max(math.ceil(math.sqrt(F) / 2.0), 1), MAX_GRID_DIM)
-            cell = ext.max() / np.float32(k) if ext.max() > 0 else np.float32(1.0)
-            inv = np.float32(1.0) / cell
-            if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
-                cell, inv = np.float32(1.0), np.float32(1.0)  # an extent too small to divide: one cell holds it all
-        cells = np.floor(ext * inv)  # fp32, like the kernel's cell index of the largest coordinate
-    if cell_size is None:
-        cells = np.minimum(cells, MAX_GRID_DIM - 1)  # only rounding can exceed it; the kernel clamps into the last cell
-    elif not np.isfinite(cells).all() or cells.max() + 1 > MAX_GRID_DIM:
-        raise ValueError(f"cell_size {cell_size!r} needs more than {MAX_GRID_DIM} cells along an axis")
-    dims = [int(c) + 1 for c in cells]
-    lo_c, dims_c = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int32 * 3)(*dims)
+        grid["keys"] = torch.empty(0, dtype=torch.int64, device=dev)
+        return grid
+    lo_c, _, _, dims_c = _grid_c(grid)
     L = lib()
     counts = torch.empty(F, dtype=torch.int64, device=dev)
-    check(L.nerf_mesh_face_cell_counts(ptr(vertices), ptr(faces), F, lo_c, float(inv), dims_c, ptr(counts), stream()),
+    check(L.nerf_mesh_face_cell_counts(ptr(vertices), ptr(faces), F, lo_c, inv, dims_c, ptr(counts), stream()),
           "nerf_mesh_face_cell_counts")
     ends = torch.cumsum(counts, 0)
     n_keys = int(ends[-1])
     if n_keys >= 2 ** 31:
         raise ValueError(f"the faces are registered in {n_keys} cells, 2^31 or more: use a larger cell_size")
     keys = torch.empty(n_keys, dtype=torch.int64, device=dev)
-    check(L.nerf_mesh_face_cell_keys(ptr(vertices), ptr(faces), F, lo_c, float(inv), dims_c, ptr(ends - counts),
-                                     ptr(keys), stream()), "nerf_mesh_face_cell_keys")
-    return {"keys": torch.sort(keys).values, "lo": lo.tolist(), "cell": float(cell), "inv": float(inv), "dims": dims,
-            "n_keys": n_keys, "F": F}
+    check(L.nerf_mesh_face_cell_keys(ptr(vertices), ptr(faces), F, lo_c, inv, dims_c, ptr(ends - counts), ptr(keys),
+                                     stream()), "nerf_mesh_face_cell_keys")
+    grid["keys"], grid["n_keys"] = torch.sort(keys).values, n_keys
+    return grid
+
+
+def _face_grid_arg(grid, F):
+    """(keys, n_keys) of a grid of mesh_face_grid; ValueError unless it is one and belongs to F faces."""
+    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
+        raise ValueError("grid must be the dict that mesh_face_grid returns")
+    n_keys = int(grid["n_keys"])
+    keys = grid["keys"]
+    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
+            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
+        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
+    if n_keys:
+        need(keys, "grid['keys']", torch.int64)
+    return keys, n_keys
 
 
 def mesh_nearest_faces(query, vertices, faces, grid, sort_queries=True, closest=True, finite_checked=False):
@@ -1126,43 +1138,26 @@ def mesh_nearest_faces(query, vertices, faces, grid, sort_queries=True, closest=
     n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
     V = _vertices_arg(vertices) if finite_checked else _finite_vertices(vertices)
     _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
-    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
-        raise ValueError("grid must be the dict that mesh_face_grid returns")
-    n_keys = int(grid["n_keys"])
-    keys = grid["keys"]
-    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
-            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
-        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
-    if n_keys:
-        need(keys, "grid['keys']", torch.int64)
+    keys, n_keys = _face_grid_arg(grid, F)
     dev = query.device
     d2 = torch.empty(n, dtype=torch.float64, device=dev)
     face = torch.empty(n, dtype=torch.int32, device=dev)
     point = torch.empty((n, 3), dtype=F32, device=dev) if closest else None
     if n == 0:
         return (d2, face, point) if closest else (d2, face)
-    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
-    cell, inv = float(grid["cell"]), float(grid["inv"])
+    grid_c = _grid_c(grid)
     L = lib()
 
     def run(q, out_d2, out_face, out_point):
         check(L.nerf_mesh_nearest_faces(ptr(q), n, ptr(keys) if n_keys else None, n_keys,
-                                        ptr(vertices) if n_keys else None, ptr(faces) if n_keys else None, F, lo_c,
-                                        cell, inv, dims_c, ptr(out_d2), ptr(out_face), ptr(out_point), stream()),
+                                        ptr(vertices) if n_keys else None, ptr(faces) if n_keys else None, F, *grid_c,
+                                        ptr(out_d2), ptr(out_face), ptr(out_point), stream()),
               "nerf_mesh_nearest_faces")
 
     if not sort_queries or n_keys == 0:
         run(query, d2, face, point)
-        return (d2, face, point) if closest else (d2, face)
-    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
-    sd2, sface = torch.empty_like(d2), torch.empty_like(face)
-    spoint = torch.empty_like(point) if closest else None
-    run(_gather3(query, order), sd2, sface, spoint)
-    order = order.to(torch.int64)
-    d2[order] = sd2
-    face[order] = sface
-    if closest:
-        point[order] = spoint
+    else:
+        _run_sorted(query, n, grid_c, (d2, face, point), run)
     return (d2, face, point) if closest else (d2, face)
 
 
@@ -1208,16 +1203,8 @@ def mesh_ray_cast(rays, vertices, faces, grid, cull_backfaces=False, finite_chec
     n = _rays_arg(rays, finite_checked)
     V = _vertices_arg(vertices)
     _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
-    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
-        raise ValueError("grid must be the dict that mesh_face_grid returns")
-    n_keys = int(grid["n_keys"])
-    keys = grid["keys"]
-    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
-            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
-        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
-    if n_keys:
-        need(keys, "grid['keys']", torch.int64)
-    cell, inv = float(grid["cell"]), float(grid["inv"])
+    keys, n_keys = _face_grid_arg(grid, F)
+    lo_c, cell, inv, dims_c = _grid_c(grid)
     c_max = float(vertices.abs().max()) if V else 0.0
     if not c_max < float("inf"):
         raise ValueError("vertices must be finite")
@@ -1230,7 +1217,6 @@ def mesh_ray_cast(rays, vertices, faces, grid, cull_backfaces=False, finite_chec
     t = torch.empty(n, dtype=torch.float64, device=dev)
     face = torch.empty(n, dtype=torch.int32, device=dev)
     bary = torch.empty((n, 2), dtype=F32, device=dev)
-    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
     check(lib().nerf_mesh_ray_cast(ptr(rays), n, ptr(keys), n_keys, ptr(vertices), ptr(faces), F, lo_c, cell, inv,
                                    dims_c, 2.0 ** -30 * c_max, int(bool(cull_backfaces)), ptr(t), ptr(face), ptr(bary),
                                    stream()), "nerf_mesh_ray_cast")
@@ -1257,37 +1243,23 @@ def mesh_point_crossings(query, vertices, faces, grid, sort_queries=True, finite
     n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
     V = _vertices_arg(vertices) if finite_checked else _finite_vertices(vertices)
     _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
-    if not isinstance(grid, dict) or not _FACE_GRID_KEYS <= set(grid):
-        raise ValueError("grid must be the dict that mesh_face_grid returns")
-    n_keys = int(grid["n_keys"])
-    keys = grid["keys"]
-    if int(grid["F"]) != F or not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or \
-            tuple(keys.shape) != (n_keys,) or (F == 0) != (n_keys == 0):
-        raise ValueError(f"grid does not belong to these faces: grid F = {grid['F']}, n_keys = {n_keys}, F = {F}")
-    if n_keys:
-        need(keys, "grid['keys']", torch.int64)
+    keys, n_keys = _face_grid_arg(grid, F)
     dev = query.device
     if F == 0 or n == 0:
         return torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
     crossings = torch.empty(n, dtype=torch.int32, device=dev)
     winding = torch.empty(n, dtype=torch.int32, device=dev)
-    lo_c, dims_c = (ctypes.c_float * 3)(*grid["lo"]), (ctypes.c_int32 * 3)(*grid["dims"])
-    cell, inv = float(grid["cell"]), float(grid["inv"])
+    grid_c = _grid_c(grid)
     L = lib()
 
     def run(q, out_c, out_w):
-        check(L.nerf_mesh_point_crossings(ptr(q), n, ptr(keys), n_keys, ptr(vertices), ptr(faces), F, lo_c, cell, inv,
-                                          dims_c, ptr(out_c), ptr(out_w), stream()), "nerf_mesh_point_crossings")
+        check(L.nerf_mesh_point_crossings(ptr(q), n, ptr(keys), n_keys, ptr(vertices), ptr(faces), F, *grid_c,
+                                          ptr(out_c), ptr(out_w), stream()), "nerf_mesh_point_crossings")
 
     if not sort_queries:
         run(query, crossings, winding)
-        return crossings, winding
-    _, order = _sorted_cell_keys(query, n, lo_c, inv, dims_c)
-    sc, sw = torch.empty_like(crossings), torch.empty_like(winding)
-    run(_gather3(query, order), sc, sw)
-    order = order.to(torch.int64)
-    crossings[order] = sc
-    winding[order] = sw
+    else:
+        _run_sorted(query, n, grid_c, (crossings, winding), run)
     return crossings, winding
 
 

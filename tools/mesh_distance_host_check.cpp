@@ -17,45 +17,15 @@
 #include <vector>
 
 #include "../nerf-sys_amd/csrc/mesh_distance_core.hpp"
+#include "mesh_host_check_common.hpp"
 
 namespace {
 
-using nerf_mm::Grid;
+using namespace mesh_check;
 
 template <class T>
 bool same_bits(T a, T b) {
   return std::memcmp(&a, &b, sizeof a) == 0;
-}
-
-struct Soup {
-  std::vector<float> v;
-  std::vector<int32_t> f;
-};
-
-// the grid of kernels.mesh_face_grid: lo = the minimum of the vertices, dims = floor((max - lo) * inv) + 1 in fp32
-bool make_grid(const std::vector<float>& p, float cell, Grid& g) {
-  const int64_t m = (int64_t)p.size() / 3;
-  g.cell = cell;
-  g.inv = 1.0f / cell;
-  for (int c = 0; c < 3; ++c) {
-    float lo = 0.0f, hi = 0.0f;
-    for (int64_t j = 0; j < m; ++j) {
-      lo = j == 0 || p[3 * j + c] < lo ? p[3 * j + c] : lo;
-      hi = j == 0 || p[3 * j + c] > hi ? p[3 * j + c] : hi;
-    }
-    g.lo[c] = lo;
-    const float cells = floorf((hi - lo) * g.inv);
-    if (!(cells + 1.0f <= (float)nerf_mm::MAX_DIM)) return false;
-    g.dims[c] = (int32_t)cells + 1;
-  }
-  return true;
-}
-
-std::vector<float> uniform(std::mt19937& rng, int64_t n, float a, float b) {
-  std::uniform_real_distribution<float> u(a, b);
-  std::vector<float> out((size_t)(3 * n));
-  for (auto& x : out) x = u(rng);
-  return out;
 }
 
 bool check(const char* name, const Soup& s, const std::vector<float>& query, float cell, std::FILE* dump = nullptr) {
@@ -106,20 +76,6 @@ bool check(const char* name, const Soup& s, const std::vector<float>& query, flo
     if (dump) std::fprintf(dump, "%a %d %a %a %a\n", got.d2, got.face, got.p[0], got.p[1], got.p[2]);
   }
   return true;
-}
-
-// a random soup with faces of a repeated index and exactly collinear corners
-Soup soup(std::mt19937& rng, int64_t V, int64_t F) {
-  Soup s;
-  s.v = uniform(rng, V, -1, 1);
-  const float line[9] = {0.25f, 0.5f, -0.5f, 0.5f, 0.5f, -0.5f, 1.0f, 0.5f, -0.5f};
-  std::copy(line, line + 9, s.v.end() - 9);
-  std::uniform_int_distribution<int32_t> vi(0, (int32_t)V - 4);
-  for (int64_t i = 0; i < 3 * F; ++i) s.f.push_back(vi(rng));
-  const int32_t dead[] = {3, 3, 9, 12, 7, 12, 20, 20, 20, (int32_t)V - 3, (int32_t)V - 2, (int32_t)V - 1,
-                          (int32_t)V - 1, (int32_t)V - 3, (int32_t)V - 2};
-  std::copy(dead, dead + 15, s.f.begin());
-  return s;
 }
 
 }  // namespace
