@@ -899,6 +899,30 @@ int nerf_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, cons
 int nerf_tsdf_face_observed(const int32_t* face_off, const float* weight, int nx, int ny, int nz, float min_weight,
                             int64_t F, uint8_t* keep, hipStream_t stream);
 
+/* TSDF fusion with colour.  color (nx,ny,nz,4) contiguous fp32, 16-byte aligned (else
+ * NERF_E_ALIGN): r, g, b and a colour weight cw per voxel; a fresh volume holds zeros.
+ * nerf_tsdf_integrate_color: nerf_tsdf_integrate's arguments, checks and rule, and rgb (n_views,H,W,3) fp32, the
+ *   colour of the pixel each depth came from.  tsdf and weight are bit for bit nerf_tsdf_integrate's.  Per voxel and
+ *   view, in the order of the views, after that view's update of (tsdf, w):
+ *   skip the colour unless the view updated the voxel and tq = s / trunc < 1 (the update was not clamped: the voxel
+ *   lies within trunc of the surface the pixel saw, so a voxel far in front of it does not take the pixel's colour);
+ *   skip unless the pixel's three channels are all finite;
+ *   c_j = (c_j cw + pixel_j) / (cw + 1) for j = r, g, b, then cw = cw + 1.
+ *   color is written only where a view coloured the voxel.  n_views = 0 launches nothing.  One thread per voxel, no
+ *   atomics; at most 8 views per launch (profiles/tsdf_color.json), the launches one after the other on the stream.
+ * nerf_tsdf_sample_color: points (N,3) -> rgb_out (N,3), cover_out (N), one thread per point.  Per axis a:
+ *   g = (x_a - lo_a) / h_a clamped to [0, n_a - 1]; i = min((int)floor(g), n_a - 2); f = g - (float)i.
+ *   Over the 8 corners c = 0..7 of the cell (i_x + (c & 1), i_y + (c >> 1 & 1), i_z + (c >> 2 & 1)):
+ *   w_a = f_a where the corner's bit of axis a is set, else 1 - f_a; tw = (w_x w_y) w_z; k = tw cw_corner;
+ *   cover = cover + k, then acc_j = acc_j + k c_j for j = r, g, b.
+ *   rgb_j = acc_j / cover where cover > 0, else 0.  A point with a NaN coordinate gets cover = 0 and rgb = 0; a point
+ *   outside the box takes the colour of the nearest point of the box.  N = 0 launches nothing. */
+int nerf_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const float* lo,
+                              const float* hi, const float* depth, const float* rgb, const float* c2w, int n_views,
+                              int H, int W, float fx, float fy, float cx, float cy, float trunc, hipStream_t stream);
+int nerf_tsdf_sample_color(const float* color, int nx, int ny, int nz, const float* lo, const float* hi,
+                           const float* points, int64_t N, float* rgb_out, float* cover_out, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -177,6 +177,8 @@ def lib():
             "nerf_box_points": [I64, U64, P, P, P, P],
             "nerf_tsdf_integrate": [P, P, I, I, I, P, P, P, P, I, I, I, F, F, F, F, F, P],
             "nerf_tsdf_face_observed": [P, P, I, I, I, F, I64, P, P],
+            "nerf_tsdf_integrate_color": [P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, F, F, F, P],
+            "nerf_tsdf_sample_color": [P, I, I, I, P, P, P, I64, P, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -244,7 +246,7 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",
            "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces",
            "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points",
-           "nerf_tsdf_integrate", "nerf_tsdf_face_observed")
+           "nerf_tsdf_integrate", "nerf_tsdf_face_observed", "nerf_tsdf_integrate_color", "nerf_tsdf_sample_color")
 
 
 def check(status: int, what: str) -> None:

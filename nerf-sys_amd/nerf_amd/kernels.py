@@ -389,15 +389,8 @@ def _f32_arg(v, name, positive):
     return f
 
 
-def tsdf_integrate(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy, trunc):
-    """Fuse depth views into a truncated signed distance volume, in place (nerf_tsdf_integrate, one launch per 8 views):
-    tsdf and
-    weight (nx,ny,nz) float32 over the lattice of mesh_extract; depth (n,H,W) or (H,W) float32, ranges along unit ray
-    directions (render_image's depth over acc, Mesh.render's depth: +inf, NaN, 0 and negative values are "no surface");
-    c2w (n,3,4), (n,4,4), (3,4) or (4,4) float32, finite, the cameras of rays_gen.  Per voxel and view, in the order of
-    the views: project to the pixel that holds the voxel, s = depth - range of the voxel, skip if s < -trunc, else
-    tsdf = (tsdf w + min(1, s / trunc)) / (w + 1), w += 1 (DESIGN §3.11.8 states every step).  n views in one call
-    are bit for bit n calls of one view.  Returns nothing.  One host read: the finiteness of c2w."""
+def _tsdf_views_args(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy, trunc):
+    """the checks of tsdf_integrate -> shape, lo, hi, depth (n,H,W), c2w (n,3|4,4), (n, H, W), (fx, fy, cx, cy, trunc)"""
     shape = _volume_arg(tsdf, "tsdf")
     _volume_arg(weight, "weight", shape)
     if tsdf.device != weight.device:
@@ -425,14 +418,99 @@ def tsdf_integrate(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy, trunc):
     fx, fy = _f32_arg(fx, "fx", True), _f32_arg(fy, "fy", True)
     cx, cy = _f32_arg(cx, "cx", False), _f32_arg(cy, "cy", False)
     trunc = _f32_arg(trunc, "trunc", True)
-    if n == 0:
-        return
+    return shape, lo, hi, depth, c2w, (n, H, W), (fx, fy, cx, cy, trunc)
+
+
+def _tsdf_rows(c2w):
+    """(n,12) contiguous rows of the 3x4 matrices; one host read: their finiteness"""
     rows = c2w[:, :3, :].contiguous()
     if not bool(torch.isfinite(rows).all()):
         raise ValueError("c2w must be finite")
+    return rows
+
+
+def tsdf_integrate(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy, trunc):
+    """Fuse depth views into a truncated signed distance volume, in place (nerf_tsdf_integrate, one launch per 8 views):
+    tsdf and
+    weight (nx,ny,nz) float32 over the lattice of mesh_extract; depth (n,H,W) or (H,W) float32, ranges along unit ray
+    directions (render_image's depth over acc, Mesh.render's depth: +inf, NaN, 0 and negative values are "no surface");
+    c2w (n,3,4), (n,4,4), (3,4) or (4,4) float32, finite, the cameras of rays_gen.  Per voxel and view, in the order of
+    the views: project to the pixel that holds the voxel, s = depth - range of the voxel, skip if s < -trunc, else
+    tsdf = (tsdf w + min(1, s / trunc)) / (w + 1), w += 1 (DESIGN §3.11.8 states every step).  n views in one call
+    are bit for bit n calls of one view.  Returns nothing.  One host read: the finiteness of c2w."""
+    shape, lo, hi, depth, c2w, (n, H, W), cam = _tsdf_views_args(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy,
+                                                                 trunc)
+    if n == 0:
+        return
+    rows = _tsdf_rows(c2w)
     lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
-    check(lib().nerf_tsdf_integrate(ptr(tsdf), ptr(weight), *shape, lo_c, hi_c, ptr(depth), ptr(rows), n, H, W, fx, fy,
-                                    cx, cy, trunc, stream()), "nerf_tsdf_integrate")
+    check(lib().nerf_tsdf_integrate(ptr(tsdf), ptr(weight), *shape, lo_c, hi_c, ptr(depth), ptr(rows), n, H, W, *cam,
+                                    stream()), "nerf_tsdf_integrate")
+
+
+def _color_volume_arg(color, shape, device):
+    need(color, "color")
+    if tuple(color.shape) != tuple(shape) + (4,):
+        raise ValueError(f"color must be {tuple(shape) + (4,)}, got {tuple(color.shape)}")
+    if color.device != device:
+        raise ValueError("color must be on the volume's device")
+    if color.data_ptr() % 16:
+        raise ValueError("color must be 16-byte aligned")
+
+
+def tsdf_integrate_color(tsdf, weight, color, lo, hi, depth, rgb, c2w, fx, fy, cx, cy, trunc):
+    """tsdf_integrate with colour, in place (nerf_tsdf_integrate_color): color (nx,ny,nz,4) float32
+    holds r, g, b and a colour weight cw per voxel (a fresh volume: zeros), rgb (n,H,W,3) or (H,W,3) float32 the colour of
+    the pixel each depth came from (render_image's rgb, Mesh.render's "color").  tsdf and weight come out bit for bit
+    as from tsdf_integrate.  Where a view updated a voxel without clamping (s / trunc < 1: within trunc of the surface
+    the pixel saw) and the pixel's three channels are finite: c = (c cw + pixel) / (cw + 1) per channel, cw += 1.
+    The other arguments, the checks and the host read are tsdf_integrate's.  Returns nothing."""
+    shape, lo, hi, depth, c2w, (n, H, W), cam = _tsdf_views_args(tsdf, weight, lo, hi, depth, c2w, fx, fy, cx, cy,
+                                                                 trunc)
+    _color_volume_arg(color, shape, tsdf.device)
+    need(rgb, "rgb")
+    if rgb.device != tsdf.device:
+        raise ValueError("rgb must be on the volume's device")
+    if rgb.dim() == 3:
+        rgb = rgb[None]
+    if tuple(rgb.shape) != (n, H, W, 3):
+        raise ValueError(f"rgb must be {(n, H, W, 3)} to match depth, got {tuple(rgb.shape)}")
+    if n == 0:
+        return
+    rows = _tsdf_rows(c2w)
+    lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    check(lib().nerf_tsdf_integrate_color(ptr(tsdf), ptr(weight), ptr(color), *shape, lo_c, hi_c, ptr(depth), ptr(rgb),
+                                          ptr(rows), n, H, W, *cam, stream()), "nerf_tsdf_integrate_color")
+
+
+def tsdf_sample_color(color, lo, hi, points):
+    """The fused colour at points (N,3) float32 (nerf_tsdf_sample_color) -> rgb (N,3), cover (N,):
+    over the 8 corners of the cell that holds the point (points outside the box are clamped onto it), each weighted by
+    its trilinear weight times its colour weight cw; cover is the sum of those weights, rgb the weighted mean where
+    cover > 0 and 0 elsewhere (no corner was ever coloured, or a coordinate is NaN)."""
+    need(color, "color")
+    if color.dim() != 4 or color.shape[3] != 4:
+        raise ValueError(f"color must be (nx,ny,nz,4), got {tuple(color.shape)}")
+    shape = tuple(int(n) for n in color.shape[:3])
+    if min(shape) < 2:
+        raise ValueError(f"every lattice dimension must be >= 2, got {shape}")
+    if shape[0] * shape[1] * shape[2] >= 2 ** 31:
+        raise ValueError(f"lattice too large: {shape} reaches 2^31 points")
+    lo, hi = _box3(lo, "lo"), _box3(hi, "hi")
+    if not all(a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"lo must be below hi on every axis, got {lo} vs {hi}")
+    need(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (N,3), got {tuple(points.shape)}")
+    if points.device != color.device:
+        raise ValueError("points must be on the volume's device")
+    N = int(points.shape[0])
+    rgb, cover = _empty((N, 3), color), _empty((N,), color)
+    lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    check(lib().nerf_tsdf_sample_color(ptr(color), *shape, lo_c, hi_c, ptr(points) if N else None, N,
+                                       ptr(rgb) if N else None, ptr(cover) if N else None, stream()),
+          "nerf_tsdf_sample_color")
+    return rgb, cover
 
 
 def tsdf_face_observed(face_off, weight, min_weight):

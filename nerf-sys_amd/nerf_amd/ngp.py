@@ -828,21 +828,26 @@ class InstantNGP(nn.Module):
         pose, fused into a TSDF volume of ``resolution`` points over ``aabb`` (default: the model's box) by
         ray_rendering.fuse_depth_views (trunc, acc_min, batch, render_kwargs as there), then
         TSDFVolume.extract_mesh (min_weight, min_faces / keep_largest, simplify, smooth as there).  normals and colors
-        as in extract_mesh: field normals and colours are evaluated at the surviving vertices."""
+        as in extract_mesh: field normals and colours are evaluated at the surviving vertices.  colors="fused" instead
+        fuses render_image's rgb alongside the depth and samples the volume's colour at the final vertices
+        (fuse_depth_views(colors=True), TSDFVolume.extract_mesh(colors="fused")): the colours the cameras saw, with
+        no query of the colour network."""
         from .ray_rendering import fuse_depth_views
         if normals not in ("field", "grid", None):
             raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
-        if colors not in (None, "linear", "srgb"):
-            raise ValueError(f"colors must be None, 'linear' or 'srgb', got {colors!r}")
+        if colors not in (None, "linear", "srgb", "fused"):
+            raise ValueError(f"colors must be None, 'linear', 'srgb' or 'fused', got {colors!r}")
+        fused = colors == "fused"
         box = self._aabb_host if aabb is None else [float(v) for v in torch.as_tensor(aabb).reshape(-1).tolist()]
         if len(box) != 6:
             raise ValueError(f"aabb must hold 6 floats (min, max), got {len(box)}")
         vol = fuse_depth_views(self, poses, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, near=near, far=far, lo=box[:3],
                                hi=box[3:], resolution=resolution, trunc=trunc, acc_min=acc_min, batch=batch,
-                               params=params, **render_kwargs)
+                               colors=fused, params=params, **render_kwargs)
         mesh = vol.extract_mesh(min_weight=min_weight, normals="grid" if normals == "grid" else None,
-                                min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth)
-        return self._mesh_attributes(mesh, normals, colors, params, chunk)
+                                min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth,
+                                colors="fused" if fused else None)
+        return self._mesh_attributes(mesh, normals, None if fused else colors, params, chunk)
 
     def _mesh_attributes(self, mesh, normals, colors, params, chunk):
         """field normals and colours at the vertices of ``mesh`` (extract_mesh, extract_mesh_tsdf)"""

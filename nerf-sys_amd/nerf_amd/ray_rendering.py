@@ -249,26 +249,33 @@ def render_image(model, *, H: int, W: int, fx: float, fy: float, cx: float, cy: 
 @torch.no_grad()
 def fuse_depth_views(model, poses: Tensor, *, H: int, W: int, fx: float, fy: float, cx: float, cy: float, near: float,
                      far: float, lo, hi, resolution, trunc: Optional[float] = None, acc_min: float = 0.5,
-                     batch: int = 8, **render_kwargs):
+                     batch: int = 8, colors: bool = False, **render_kwargs):
     """Render depth from every pose (n,3,4) or (n,4,4) with render_image and fuse it into a tsdf.TSDFVolume over the
     box [lo, hi].  render_image's depth is sum w t, not normalised by the hit probability: the fused
     range is depth / acc where acc > acc_min and +inf ("nothing seen") elsewhere.  The views are integrated ``batch``
     at a time, one call of TSDFVolume.integrate each.  Works for any model render_image takes (an expert, the vanilla network, the MoE
-    container); render_kwargs go to render_image."""
+    container); render_kwargs go to render_image.
+    colors=True gives a volume with colour and fuses render_image's rgb alongside the depth (tsdf and
+    weight are the same bits either way).  That rgb is composited over bg_color_default: a pixel whose acc lies
+    between acc_min and 1 carries a share 1 - acc of the background into the fused colour; it is not
+    un-premultiplied."""
     from .tsdf import TSDFVolume
     if batch < 1:
         raise ValueError(f"batch must be positive, got {batch}")
     if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):
         raise ValueError("poses must be a (n,3,4) or (n,4,4) tensor")
     device = next(model.parameters()).device
-    vol = TSDFVolume(lo, hi, resolution, trunc=trunc, device=device)
+    vol = TSDFVolume(lo, hi, resolution, trunc=trunc, device=device, color=bool(colors))
     poses = poses[:, :3, :].to(device=device, dtype=torch.float32).contiguous()
     for s in range(0, poses.shape[0], batch):
-        views = []
+        views, rgbs = [], []
         for c2w in poses[s:s + batch]:
-            _, depth, acc = render_image(model, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, c2w=c2w, near=near, far=far,
-                                         **render_kwargs)
+            rgb, depth, acc = render_image(model, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, c2w=c2w, near=near, far=far,
+                                           **render_kwargs)
             depth, acc = depth.float().view(H, W), acc.float().view(H, W)
             views.append(torch.where(acc > acc_min, depth / acc, torch.full_like(depth, float("inf"))))
-        vol.integrate(torch.stack(views), fx, fy, cx, cy, poses[s:s + batch])
+            if colors:
+                rgbs.append(rgb)
+        vol.integrate(torch.stack(views), fx, fy, cx, cy, poses[s:s + batch],
+                      rgb=torch.stack(rgbs) if colors else None)
     return vol

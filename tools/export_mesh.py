@@ -59,6 +59,12 @@ needs for its faces to be kept.  Every option and report above works on it; the 
 "tsdf_min_weight".
 
   python tools/export_mesh.py --train-steps 2000 --tsdf 32 --report-depth 4 --out mesh.ply
+
+--colors fused (with --tsdf only, an error otherwise) fuses the colour of the rendered views alongside their depth and
+colours every vertex from the volume instead of querying the colour network: the route that also
+works for models without such a query.  The first JSON line then says "colors": "fused".
+
+  python tools/export_mesh.py --train-steps 2000 --tsdf 32 --colors fused --out mesh.ply
 """
 import argparse
 import json
@@ -91,8 +97,9 @@ def main():
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--threshold", type=float, default=10.0)
     ap.add_argument("--normals", default="field", choices=["field", "grid", "none"])
-    ap.add_argument("--colors", default="none", choices=["none", "linear", "srgb"],
-                    help="vertex colours from the colour network, seen head-on along the field normal")
+    ap.add_argument("--colors", default="none", choices=["none", "linear", "srgb", "fused"],
+                    help="vertex colours from the colour network, seen head-on along the field normal; fused (with "
+                         "--tsdf): the colours of the rendered views, fused in the volume")
     flt = ap.add_mutually_exclusive_group()
     flt.add_argument("--min-faces", type=int, default=None, help="drop connected components with fewer faces")
     flt.add_argument("--keep-largest", type=int, default=None, help="keep the K components with the most faces")
@@ -116,6 +123,8 @@ def main():
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
+    if a.colors == "fused" and not a.tsdf:
+        ap.error("--colors fused needs --tsdf VIEWS: the colours are fused from the rendered views")
     if not torch.cuda.is_available():
         raise SystemExit("export_mesh: needs a GPU (no CPU fallback)")
     from nerf_amd.ngp import InstantNGP
