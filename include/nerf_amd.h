@@ -703,7 +703,20 @@ int nerf_mesh_remap_faces(const int32_t* faces, const int32_t* keep32, const int
  *   rotation with the smallest index first; the cyclic order, hence the orientation, is kept: a face and its mirror
  *   image are different forms).  A remap pass, an insert of the non-degenerate faces into a hash set of face indices
  *   keyed by the canonical triple read through the index, and a lookup: 3 launches.  faces_out must not alias faces.
- *   The result goes to nerf_mesh_mark_used / nerf_mesh_remap_faces with keep as the per-face flag. */
+ *   The result goes to nerf_mesh_mark_used / nerf_mesh_remap_faces with keep as the per-face flag.
+ * nerf_mesh_cluster_quadric: the quadric-error position of every cluster in place of the mean.  faces (F,3) are the
+ *   ORIGINAL faces; (row_off (V+1), col) is the vertex-to-face adjacency (nerf_mesh_pair_keys mode 1 ...
+ *   nerf_mesh_csr_build) of faces_out of nerf_mesh_cluster_faces, so row r of a representative lists, ascending and
+ *   once each, the original faces with a corner in cluster r; mean (V,3) is out_vertices of nerf_mesh_cluster_reduce;
+ *   tol in (0, 1), else NERF_E_ARG.  In the frame of the representative's cell (centre c = lo + (i + 0.5) cell,
+ *   y = (p - c) / cell, all in double, every operation rounded on its own) the row's faces are summed in the row's
+ *   order into A += L m m^T, b += (L d) m with n = (b - a) x (c - a), L = |n|, m = n / L, d = -(m . a); faces with
+ *   L == 0 are skipped.  8 cyclic Jacobi sweeps give the eigenpairs of A; from x = the mean's local coordinates,
+ *   x += ((e_i . g) / l_i) e_i for i = 0, 1, 2 with l_i > tol max|l| and g = -b - A x.  out_position[r] =
+ *   float(c + x cell) and out_placed[r] = 1 when max|l| > 0 and x is finite and inside [-0.5, 0.5]^3, else
+ *   out_position[r] = mean[r] bit for bit and out_placed[r] = 0; both are zeros at the rows that are no
+ *   representative.  out_position must alias neither mean nor vertices.  One thread per vertex row, one launch, no
+ *   workspace, no atomics; it allocates nothing and does not synchronise. */
 int64_t nerf_mesh_cluster_labels_workspace_bytes(int64_t V, int table_log2);
 int nerf_mesh_cluster_labels(const float* vertices, int64_t V, const float* lo, float cell, float inv,
                              const int32_t* dims, int table_log2, void* workspace, int64_t workspace_bytes,
@@ -717,6 +730,10 @@ int64_t nerf_mesh_cluster_faces_workspace_bytes(int64_t F, int table_log2);
 int nerf_mesh_cluster_faces(const int32_t* faces, const int32_t* labels, int64_t F, int64_t V, int table_log2,
                             void* workspace, int64_t workspace_bytes, int32_t* faces_out, uint8_t* keep,
                             int32_t* status, hipStream_t stream);
+int nerf_mesh_cluster_quadric(const float* vertices, const int32_t* faces, const int32_t* labels,
+                              const int32_t* row_off, const int32_t* col, const float* mean, int64_t V, int64_t F,
+                              const float* lo, float cell, float inv, const int32_t* dims, double tol,
+                              float* out_position, uint8_t* out_placed, hipStream_t stream);
 
 /* Mesh smoothing: two CSR adjacencies built from sorted int64 keys, a Jacobi smoothing pass over the
  * first and face-derived vertex normals over the second.  faces (F,3) int32 with 0 <= index < V: ANY indexed triangle

@@ -15,11 +15,16 @@
 //     2. insert    one thread per non-degenerate face: the hash set of face indices (slot key = the canonical triple
 //                  of faces_out[slot value], written by the launch before).
 //     3. lookup    one thread per face: keep[f] = non-degenerate && slot value == f.
+//   nerf_mesh_cluster_quadric  the quadric-error position of every cluster (mesh_quadric_core.hpp).
+//     1. place     one thread per vertex row: a representative sums the plane quadrics of its row of the
+//                  vertex-to-face adjacency in the row's order, solves from the mean and stores its position and flag;
+//                  every other row stores zeros.  No atomics, one writer per element.
 //   status[0] != 0 reports a thread that exhausted its probe bound; status[1] is the longest probe chain.
 //
 // The kernels do not check indices or finiteness: that is the caller's duty (kernels.py validates before launching).
 #include "common.hpp"
 #include "mesh_grid_host.hpp"
+#include "mesh_quadric_core.hpp"
 #include "mesh_simplify_core.hpp"
 
 namespace {
@@ -208,6 +213,17 @@ __global__ __launch_bounds__(NTHREADS) void faces_lookup_kernel(const int32_t* _
   report(status, ok, probes, 2);
 }
 
+// ---------------------------------------------------------------- quadric placement
+
+__global__ __launch_bounds__(NTHREADS) void cluster_quadric_kernel(
+    const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ labels,
+    const int32_t* __restrict__ row_off, const int32_t* __restrict__ col, const float* __restrict__ mean, int64_t V,
+    Grid g, double tol, float* __restrict__ out_pos, uint8_t* __restrict__ out_placed) {
+  const int64_t v = (int64_t)blockIdx.x * NTHREADS + threadIdx.x;
+  if (v >= V) return;
+  nerf_mq::place_vertex(verts, faces, labels, row_off, col, mean, g, tol, v, out_pos, out_placed);
+}
+
 bool sizes_ok(int64_t F, int64_t V) { return F >= 0 && V >= 0 && V < nerf_grid::LIMIT && 3 * F < nerf_grid::LIMIT; }
 
 bool table_ok(int64_t items, int table_log2) {
@@ -310,5 +326,21 @@ extern "C" int nerf_mesh_cluster_faces(const int32_t* faces, const int32_t* labe
   faces_remap_kernel<<<fb, NTHREADS, 0, stream>>>(faces, labels, F, faces_out);
   faces_insert_kernel<<<fb, NTHREADS, 0, stream>>>(faces_out, F, table, mask, status);
   faces_lookup_kernel<<<fb, NTHREADS, 0, stream>>>(faces_out, F, table, mask, keep, status);
+  return nerf_launch_status();
+}
+
+extern "C" int nerf_mesh_cluster_quadric(const float* vertices, const int32_t* faces, const int32_t* labels,
+                                         const int32_t* row_off, const int32_t* col, const float* mean, int64_t V,
+                                         int64_t F, const float* lo, float cell, float inv, const int32_t* dims,
+                                         double tol, float* out_position, uint8_t* out_placed, hipStream_t stream) {
+  NERF_CHECK_ARG(sizes_ok(F, V) && grid_ok(lo, cell, inv, dims));
+  NERF_CHECK_ARG(tol > 0.0 && tol < 1.0);  // false for a NaN
+  if (V == 0) return NERF_OK;
+  NERF_CHECK_ARG(vertices && labels && row_off && mean && out_position && out_placed);  // col NULL: every row empty
+  NERF_CHECK_ARG(F == 0 || faces);
+  NERF_CHECK_ARG(out_position != mean && out_position != vertices);
+  const Grid g = nerf_grid::fill_grid(lo, cell, inv, dims);
+  cluster_quadric_kernel<<<(unsigned)nerf_cdiv(V, NTHREADS), NTHREADS, 0, stream>>>(
+      vertices, faces, labels, row_off, col, mean, V, g, tol, out_position, out_placed);
   return nerf_launch_status();
 }

@@ -160,6 +160,7 @@ def lib():
             "nerf_mesh_cluster_reduce": [P, P, P, P, I64, P, F, F, P, P, I64, P, P, P, P],
             "nerf_mesh_cluster_faces_workspace_bytes": [I64, I],
             "nerf_mesh_cluster_faces": [P, P, I64, I64, I, P, I64, P, P, P, P],
+            "nerf_mesh_cluster_quadric": [P, P, P, P, P, P, I64, I64, P, F, F, P, D, P, P, P],
             "nerf_mesh_pair_keys": [P, I64, I, P, P],
             "nerf_mesh_csr_flags": [P, I64, P, P, P],
             "nerf_mesh_csr_build": [P, I64, P, P, I64, I64, P, P, P],
@@ -241,6 +242,7 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_remap_faces", "nerf_mesh_cluster_labels_workspace_bytes", "nerf_mesh_cluster_labels",
            "nerf_mesh_cluster_reduce_workspace_bytes", "nerf_mesh_cluster_reduce",
            "nerf_mesh_cluster_faces_workspace_bytes", "nerf_mesh_cluster_faces",
+           "nerf_mesh_cluster_quadric",
            "nerf_mesh_pair_keys", "nerf_mesh_csr_flags", "nerf_mesh_csr_build", "nerf_mesh_smooth_pass",
            "nerf_mesh_vertex_normals",
            "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",

@@ -765,14 +765,59 @@ def mesh_cluster_faces(faces, labels, table_log2=None, return_probes=False, rang
     return (out, keep, probes) if return_probes else (out, keep)
 
 
+def _tol_arg(tol):
+    try:
+        t = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"tol must be a float, got {tol!r}") from None
+    if not 0.0 < t < 1.0:  # false for a NaN
+        raise ValueError(f"tol must be a finite float in (0, 1), got {tol!r}")
+    return t
+
+
+def mesh_cluster_quadric(vertices, faces, labels, row_off, col, mean, lo, cell, dims, tol=1e-3, ranges_checked=False):
+    """Vertex clustering, quadric-error placement (nerf_mesh_cluster_quadric): the cluster's vertex at the point that
+    minimises the summed plane quadrics of the faces that touch the cluster, in place of the members' mean.  vertices
+    (V,3) float32, finite, and faces (F,3) int32 of the ORIGINAL mesh; labels (V,) int32 of mesh_cluster_labels;
+    (row_off, col) = mesh_vertex_faces(faces', V) on the faces' of mesh_cluster_faces, so that the row of a
+    representative lists the original faces with a corner in its cluster; mean (V,3) float32, the positions of
+    mesh_cluster_reduce; the grid as there.  In the frame of the representative's cell (the box [-0.5, 0.5]^3) the
+    row's faces are summed in the row's order, weighted by twice their area; 8 cyclic Jacobi sweeps give the
+    eigenpairs, and from the mean the solve moves only along eigenvectors whose eigenvalue exceeds ``tol`` times the
+    largest (Lindstrom's 1e-3): a flat cluster's vertex is the mean projected onto its plane, an edge cluster's onto
+    the edge, a corner cluster's is the corner.  A cluster without a face of positive area, and one whose solution is
+    not finite or leaves the cell, keeps the mean bit for bit.  Returns position (V,3) float32 and placed (V,) uint8
+    (1 where the solution was accepted), both zeros at the rows that are no representative.  All in double, every
+    operation rounded on its own, so bitwise reproducible.  ValueError before any launch on a wrong dtype, shape or
+    device and on a ``tol`` outside (0, 1).  Host reads: the index ranges of faces, labels and of the adjacency
+    (skipped with ``ranges_checked``)."""
+    V = _vertices_arg(vertices)
+    need(labels, "labels", torch.int32)
+    _, F = _smooth_faces_arg(faces, V, ranges_checked, labels=labels)
+    lo_c, cell32, inv, dims_c = _grid_arg(lo, cell, dims)
+    _csr_arg(row_off, col, V, F, ranges_checked)
+    need(mean, "mean")
+    if tuple(mean.shape) != (V, 3):
+        raise ValueError(f"mean must be ({V},3), got {tuple(mean.shape)}")
+    t = _tol_arg(tol)
+    position = torch.empty_like(vertices)
+    placed = torch.empty(V, dtype=torch.uint8, device=vertices.device)
+    if V:
+        check(lib().nerf_mesh_cluster_quadric(ptr(vertices), ptr(faces) if F else None, ptr(labels), ptr(row_off),
+                                              ptr(col) if col.numel() else None, ptr(mean), V, F, lo_c, cell32, inv,
+                                              dims_c, t, ptr(position), ptr(placed), stream()),
+              "nerf_mesh_cluster_quadric")
+    return position, placed
+
+
 # ------------------------------------------------------------------ mesh smoothing (DESIGN §3.11.3)
 
 
-def _smooth_faces_arg(faces, n_vertices, ranges_checked=False):
+def _smooth_faces_arg(faces, n_vertices, ranges_checked=False, labels=None):
     """_faces_arg with the tighter size limit of the adjacency build: 6 F below 2^31 (the int32 scan of the flags)."""
     if isinstance(faces, torch.Tensor) and faces.dim() == 2 and 6 * int(faces.shape[0]) >= 2 ** 31:
         raise ValueError(f"6 * F must be below 2^31, got F = {int(faces.shape[0])}")
-    return _faces_arg(faces, n_vertices, ranges_checked=ranges_checked)
+    return _faces_arg(faces, n_vertices, labels, ranges_checked)
 
 
 def _csr(faces, V, F, mode, boundary=False):

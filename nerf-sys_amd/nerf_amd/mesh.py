@@ -166,15 +166,24 @@ class Mesh:
 
     # ---- simplification on the device (kernels.mesh_cluster_*)
 
-    def simplify(self, cell_size, *, origin=None) -> "Mesh":
+    def simplify(self, cell_size, *, origin=None, placement="mean", tol=1e-3) -> "Mesh":
         """Vertex clustering: snap the vertices to a grid of cubic cells of edge ``cell_size`` (world units) whose
         corner is ``origin`` (3 floats; default: the minimum of the vertices), replace every occupied cell by one
         vertex at the mean of its members (normals: the normalised sum, colours: the mean), rewrite the faces, and
         drop the faces that collapsed and the later copies of a face.  Kept faces stay in their order, the surviving
         vertices are ordered by the smallest vertex index of their cell; cells and vertices that no surviving face
-        uses are dropped.  A tiny cell welds coincident vertices and removes zero-area triangles.  Bitwise
-        reproducible.  ValueError on a ``cell_size`` that is not a finite positive float, on non-finite vertices, and
-        on a grid of more than 2^20 cells along an axis."""
+        uses are dropped.  A tiny cell welds coincident vertices and removes zero-area triangles.  ``placement``:
+        "mean" (the default) or "quadric".  "quadric" moves every cluster's vertex to the point that minimises the
+        summed plane quadrics of the original faces that touch the cluster (kernels.mesh_cluster_quadric), solved from
+        the mean and only along the directions whose eigenvalue exceeds ``tol`` (in (0, 1)) times the largest: flat
+        regions stay in their plane, edges and corners are kept, a convex surface does not shrink; a vertex never
+        leaves its cell, and a cluster without a usable solution keeps the mean.  Faces, normals and colours are the
+        same for both placements.  Bitwise reproducible.  ValueError on a ``cell_size`` that is not a finite positive
+        float, on another ``placement``, on a ``tol`` outside (0, 1), on non-finite vertices, and on a grid of more
+        than 2^20 cells along an axis."""
+        if placement not in ("mean", "quadric"):
+            raise ValueError(f'placement must be "mean" or "quadric", got {placement!r}')
+        tol = K._tol_arg(tol)
         with np.errstate(all="ignore"):
             cell = np.float32(cell_size)
             inv = np.float32(1.0) / cell
@@ -207,6 +216,10 @@ class Mesh:
         cv, cn, cc = K.mesh_cluster_reduce(v, labels, lo.tolist(), cell, dims, normals=self.normals, colors=self.colors,
                                            ranges_checked=True)
         faces, keep = K.mesh_cluster_faces(f, labels, ranges_checked=True)
+        if placement == "quadric":
+            row_off, col = K.mesh_vertex_faces(faces, v.shape[0], ranges_checked=True)
+            cv, _ = K.mesh_cluster_quadric(v, f, labels, row_off, col, cv, lo.tolist(), cell, dims, tol=tol,
+                                           ranges_checked=True)
         ov, of, out = K.mesh_compact(cv, faces, keep, [a for a in (cn, cc) if a is not None], ranges_checked=True)
         out = iter(out)
         return Mesh(ov, of, None if cn is None else next(out), None if cc is None else next(out))
@@ -467,14 +480,16 @@ def density_lattice(density_fn: Callable, lo, hi, resolution: Union[int, Sequenc
 def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[int]], threshold: float,
                  normals: Union[str, None, Callable] = "grid", chunk: int = 2 ** 20, device=None,
                  min_faces: Optional[int] = None, keep_largest: Optional[int] = None,
-                 simplify: Optional[float] = None, smooth: Optional[int] = None) -> Mesh:
+                 simplify: Optional[float] = None, smooth: Optional[int] = None,
+                 simplify_placement: str = "mean") -> Mesh:
     """The level set density_fn = threshold inside the box [lo, hi] as a Mesh on the device.  normals: "grid" (the
     lattice's central differences, from the extraction kernel), None, or a callable evaluated at the vertices
     ((V,3) -> (V,3)).  min_faces / keep_largest (at most one): Mesh.filter_components on the extracted surface, before
     a callable ``normals`` is evaluated, so that it runs on the surviving vertices only.  simplify: a cell size in
     world units for Mesh.simplify, applied after the component filter and also before a callable ``normals``; "grid"
-    normals are averaged per cell by the clustering kernel.  smooth: a number of Taubin iterations for Mesh.smooth with
-    its defaults, applied after ``simplify`` and also before a callable ``normals``; "grid" normals are then replaced
+    normals are averaged per cell by the clustering kernel.  simplify_placement: "mean" or "quadric", the ``placement``
+    of Mesh.simplify (quadric-error vertices keep edges, corners and volume; faces and attributes are the same).
+    smooth: a number of Taubin iterations for Mesh.smooth with its defaults, applied after ``simplify`` and also before a callable ``normals``; "grid" normals are then replaced
     by the face-derived normals of the smoothed mesh (Mesh.compute_normals).  None returns the surface unsmoothed."""
     if not (normals is None or normals == "grid" or callable(normals)):
         raise ValueError(f"normals must be 'grid', None or a callable, got {normals!r}")
@@ -482,13 +497,15 @@ def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[i
         raise ValueError(f"smooth must be None or an int >= 0, got {smooth!r}")
     if min_faces is not None and keep_largest is not None:
         raise ValueError("give at most one of min_faces and keep_largest")
+    if simplify_placement not in ("mean", "quadric"):
+        raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
     lo, hi = _box(lo, hi)
     field = density_lattice(density_fn, lo, hi, resolution, chunk=chunk, device=device)
     mesh = Mesh(*K.mesh_extract(field, threshold, lo, hi, normals=(normals == "grid")))
     if min_faces is not None or keep_largest is not None:
         mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
     if simplify is not None:
-        mesh = mesh.simplify(simplify)
+        mesh = mesh.simplify(simplify, placement=simplify_placement)
     if smooth is not None:
         mesh = mesh.smooth(smooth)
     if callable(normals):

@@ -795,7 +795,7 @@ class InstantNGP(nn.Module):
 
     def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
                      chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None, simplify=None,
-                     smooth=None):
+                     smooth=None, simplify_placement="mean"):
         """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
         (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
         (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
@@ -805,8 +805,11 @@ class InstantNGP(nn.Module):
         the networks run on the surviving vertices only.  simplify: a cell size in world units for Mesh.simplify
         (vertex clustering), applied after that filter and likewise before field normals and colours.  smooth: a
         number of Taubin iterations for Mesh.smooth, applied after ``simplify``: field normals and colours are then
-        evaluated at the smoothed vertices, and "grid" normals become the face-derived normals of the smoothed mesh."""
+        evaluated at the smoothed vertices, and "grid" normals become the face-derived normals of the smoothed mesh.
+        simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify (quadric-error vertices)."""
         from .mesh import extract_mesh
+        if simplify_placement not in ("mean", "quadric"):
+            raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         if normals not in ("field", "grid", None):
             raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
         if colors not in (None, "linear", "srgb"):
@@ -817,13 +820,13 @@ class InstantNGP(nn.Module):
         mesh = extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold,
                             normals="grid" if normals == "grid" else None, chunk=chunk,
                             device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest,
-                            simplify=simplify, smooth=smooth)
+                            simplify=simplify, smooth=smooth, simplify_placement=simplify_placement)
         return self._mesh_attributes(mesh, normals, colors, params, chunk)
 
     def extract_mesh_tsdf(self, poses, H, W, fx, fy, cx, cy, near, far, resolution=256, aabb=None, trunc=None,
                           acc_min: float = 0.5, min_weight=1, normals="field", colors=None, min_faces=None,
                           keep_largest=None, simplify=None, smooth=None, params=None, chunk: int = 2 ** 20,
-                          batch: int = 8, **render_kwargs):
+                          batch: int = 8, simplify_placement="mean", **render_kwargs):
         """The surface the cameras ``poses`` (n,3,4) see, as a mesh.Mesh on the device: render_image's depth from every
         pose, fused into a TSDF volume of ``resolution`` points over ``aabb`` (default: the model's box) by
         ray_rendering.fuse_depth_views (trunc, acc_min, batch, render_kwargs as there), then
@@ -831,7 +834,9 @@ class InstantNGP(nn.Module):
         as in extract_mesh: field normals and colours are evaluated at the surviving vertices.  colors="fused" instead
         fuses render_image's rgb alongside the depth and samples the volume's colour at the final vertices
         (fuse_depth_views(colors=True), TSDFVolume.extract_mesh(colors="fused")): the colours the cameras saw, with
-        no query of the colour network."""
+        no query of the colour network.  simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify."""
+        if simplify_placement not in ("mean", "quadric"):
+            raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         from .ray_rendering import fuse_depth_views
         if normals not in ("field", "grid", None):
             raise ValueError(f"normals must be 'field', 'grid' or None, got {normals!r}")
@@ -846,7 +851,7 @@ class InstantNGP(nn.Module):
                                colors=fused, params=params, **render_kwargs)
         mesh = vol.extract_mesh(min_weight=min_weight, normals="grid" if normals == "grid" else None,
                                 min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth,
-                                colors="fused" if fused else None)
+                                colors="fused" if fused else None, simplify_placement=simplify_placement)
         return self._mesh_attributes(mesh, normals, None if fused else colors, params, chunk)
 
     def _mesh_attributes(self, mesh, normals, colors, params, chunk):

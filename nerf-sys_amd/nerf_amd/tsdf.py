@@ -85,13 +85,17 @@ class TSDFVolume:
 
     def extract_mesh(self, min_weight=1, normals: Optional[str] = "grid", min_faces: Optional[int] = None,
                      keep_largest: Optional[int] = None, simplify: Optional[float] = None,
-                     smooth: Optional[int] = None, colors: Optional[str] = None) -> Mesh:
+                     smooth: Optional[int] = None, colors: Optional[str] = None,
+                     simplify_placement: str = "mean") -> Mesh:
         """The zero level of the fused field as a Mesh: mesh_extract(-tsdf, 0) (inside is tsdf < 0, normals point to
         larger tsdf: outwards), then only the faces of cells whose 8 corners all have weight >= min_weight
         (min_weight = 0 keeps every face, the sheet at -trunc behind the surface included), then the options of
         mesh.extract_mesh in its order: min_faces / keep_largest (at most one), simplify, smooth.  colors: None, or
         "fused" on a volume with colour: sample_colors at the final vertices, after the filters, simplify and smooth,
-        as Mesh.colors (0.5 where no view coloured a corner of the vertex's cell)."""
+        as Mesh.colors (0.5 where no view coloured a corner of the vertex's cell).  simplify_placement: "mean" or
+        "quadric", the ``placement`` of Mesh.simplify."""
+        if simplify_placement not in ("mean", "quadric"):
+            raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         if normals not in ("grid", None):
             raise ValueError(f"normals must be 'grid' or None, got {normals!r}")
         if colors not in ("fused", None):
@@ -110,7 +114,7 @@ class TSDFVolume:
         if min_faces is not None or keep_largest is not None:
             mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
         if simplify is not None:
-            mesh = mesh.simplify(simplify)
+            mesh = mesh.simplify(simplify, placement=simplify_placement)
         if smooth is not None:
             mesh = mesh.smooth(smooth)
         if colors == "fused":

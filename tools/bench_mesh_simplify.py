@@ -11,6 +11,12 @@ gate: there is no earlier implementation to compare with.
             compact            kernels.mesh_compact of the clustered vertices, remapped faces and keep flags
             simplify           Mesh.simplify as a whole (the min / max read, two status reads, the compaction's read)
             filter_components  Mesh.filter_components(min_faces=...) on the same mesh, for context
+            with --placement quadric ("Quadric placement"), on the same meshes by the same method:
+            csr_build          kernels.mesh_vertex_faces of the remapped faces (keys, torch.sort, flags, scan, one
+                               host read, row build): the lists of faces per cluster
+            quadric_kernel     nerf_mesh_cluster_quadric alone (one launch)
+            simplify_quadric   Mesh.simplify(placement="quadric") as a whole, next to ``simplify`` (the mean placement,
+                               which is what Mesh.simplify did before the option existed)
   bytes     for the three kernel groups the traffic the method implies at the least, next to the practical HBM rate
             DESIGN uses (about 5 TB/s).  labels: 12 V read, keys written and read twice (24 V), the table cleared and
             one slot per vertex touched twice (4 T + 8 V), labels written (4 V): 48 V + 4 T.  reduce with normals:
@@ -24,6 +30,7 @@ is reported with the fastest and slowest; the phases are alternated inside every
 Prints one JSON line and writes it to --out.
 
   python tools/bench_mesh_simplify.py [--sizes 128 256 512] [--noise-size 128] [--factor 2] [--rounds R] [--out FILE]
+  python tools/bench_mesh_simplify.py --placement quadric     (writes profiles/mesh_simplify_quadric.json)
 """
 import argparse
 import ctypes
@@ -88,10 +95,28 @@ def bench_one(name, field, iso, n, a, dev):
     again = K.mesh_compact(cv, faces2, keep, [cn], ranges_checked=True)
     same = bool(torch.equal(again[0], out.vertices) and torch.equal(again[1], out.faces) and
                 torch.equal(again[2][0], out.normals))
+    quadric = {}
+    if a.placement == "quadric":
+        out_q = mesh.simplify(cell, placement="quadric")
+        row_off, col = K.mesh_vertex_faces(faces2, V, ranges_checked=True)
+        pos = torch.empty_like(mesh.vertices)
+        placed = torch.empty(V, dtype=torch.uint8, device=dev)
+
+        def quadric_kernel():
+            check(L.nerf_mesh_cluster_quadric(ptr(mesh.vertices), ptr(mesh.faces), ptr(labels), ptr(row_off), ptr(col),
+                                              ptr(cv), V, F, lo_c, float(cell), float(inv), dims_c, 1e-3, ptr(pos),
+                                              ptr(placed), stream()), "quadric")
+
+        quadric_kernel()
+        again_q = K.mesh_compact(pos, faces2, keep, [cn], ranges_checked=True)
+        same = same and bool(torch.equal(again_q[0], out_q.vertices) and torch.equal(again_q[1], out_q.faces))
+        quadric = {"csr_build": lambda: K.mesh_vertex_faces(faces2, V, ranges_checked=True),
+                   "quadric_kernel": quadric_kernel,
+                   "simplify_quadric": lambda: mesh.simplify(cell, placement="quadric")}
     res = timed({"labels_kernels": labels_kernels, "reduce_kernels": reduce_kernels, "faces_kernels": faces_kernels,
                  "compact": lambda: K.mesh_compact(cv, faces2, keep, [cn], ranges_checked=True),
                  "simplify": lambda: mesh.simplify(cell),
-                 "filter_components": lambda: mesh.filter_components(min_faces=a.min_faces)},
+                 "filter_components": lambda: mesh.filter_components(min_faces=a.min_faces), **quadric},
                 a.rounds, a.inner, a.warmup)
     eff = {"labels_kernels": 48 * V + 4 * (1 << kv), "reduce_kernels": 172 * V,
            "faces_kernels": 69 * F + 4 * (1 << kf)}
@@ -104,6 +129,12 @@ def bench_one(name, field, iso, n, a, dev):
                 "table_log2_vertices": kv, "table_log2_faces": kf, "longest_probe_chain_vertices": probes_v,
                 "longest_probe_chain_faces": probes_f, "clusters": int((labels == torch.arange(
                     V, dtype=torch.int32, device=dev)).sum()), "pieces_equal_simplify": same})
+    if quadric:
+        rows = (row_off[1:] - row_off[:-1])
+        rep = labels == torch.arange(V, dtype=torch.int32, device=dev)
+        res.update({"csr_entries": int(col.shape[0]), "longest_row": int(rows.max()),
+                    "clusters_placed": int(placed.sum()), "clusters_kept_mean": int(rep.sum()) - int(placed.sum()),
+                    "volume_in": mesh.volume(), "volume_mean": out.volume(), "volume_quadric": out_q.volume()})
     return res
 
 
@@ -117,8 +148,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--inner", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_simplify.json"))
+    ap.add_argument("--placement", choices=["mean", "quadric"], default="mean",
+                    help="quadric: also time the CSR build, the quadric kernel and Mesh.simplify(placement='quadric')")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mesh_simplify_quadric.json" if a.placement == "quadric"
+                             else "mesh_simplify.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_mesh_simplify: needs a GPU (timings on a CPU say nothing about the MI355X)")
     dev = torch.device("cuda:0")
@@ -128,7 +164,8 @@ def main():
         g = torch.Generator(device="cpu").manual_seed(18)
         noise = (torch.rand((n, n, n), generator=g) * 2.0 - 1.0).to(dev).contiguous()
         runs.append(bench_one(f"noise{n}", noise, a.noise_threshold, n, a, dev))
-    res = {"bench": "mesh_simplify", "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "inner": a.inner,
+    res = {"bench": "mesh_simplify" if a.placement == "mean" else "mesh_simplify_quadric",
+           "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "inner": a.inner,
            "factor": a.factor, "hbm_practical_tb_per_s": HBM_PRACTICAL_TBS, "meshes": runs}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -22,6 +22,13 @@ The JSON line then also reports the faces before the clustering.
 
   python tools/export_mesh.py --train-steps 2000 --min-faces 200 --simplify 0.02 --out mesh.ply
 
+--simplify-placement quadric puts every cluster's vertex at the minimum of the summed plane quadrics of the faces that
+touch the cluster instead of at the members' mean (Mesh.simplify(placement="quadric")): edges, corners and the enclosed
+volume are kept, the faces are the same.  The default, mean, changes nothing; with quadric the JSON line also carries
+"simplify_placement".
+
+  python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --simplify-placement quadric --out mesh.ply
+
 --smooth N runs N Taubin iterations on the device (Mesh.smooth) after the filter and the clustering and
 before normals and colours are evaluated; "grid" normals become the face-derived normals of the smoothed surface.
 
@@ -105,6 +112,8 @@ def main():
     flt.add_argument("--keep-largest", type=int, default=None, help="keep the K components with the most faces")
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL",
                     help="vertex clustering with cells of this edge (world units)")
+    ap.add_argument("--simplify-placement", choices=["mean", "quadric"], default="mean",
+                    help="where --simplify puts a cluster's vertex: the members' mean or the quadric-error minimum")
     ap.add_argument("--smooth", type=int, default=None, metavar="N", help="Taubin smoothing iterations")
     ap.add_argument("--report-error", action="store_true",
                     help="also print the distance between the surface before --simplify / --smooth and the exported one")
@@ -168,7 +177,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mesh = extract(normals=None if a.normals == "none" else a.normals, colors=None if a.colors == "none" else a.colors,
-                   min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify, smooth=a.smooth)
+                   min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify, smooth=a.smooth,
+                   simplify_placement=a.simplify_placement)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mesh.save_ply(a.out)
@@ -188,6 +198,7 @@ def main():
                       "smooth": a.smooth,
                       "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
                       "extract_seconds": round(dt, 4), "out": a.out,
+                      **({"simplify_placement": a.simplify_placement} if a.simplify_placement != "mean" else {}),
                       **({"tsdf": a.tsdf, "tsdf_min_weight": a.tsdf_min_weight} if a.tsdf else {})}))
     if a.report_error:
         # the surface the clustering and the smoothing started from: extracted again, filtered, nothing else
