@@ -891,6 +891,35 @@ int nerf_mesh_point_crossings(const float* query, int64_t n, const int64_t* sort
                               hipStream_t stream);
 int nerf_box_points(int64_t n, uint64_t seed, const float* lo, const float* hi, float* points, hipStream_t stream);
 
+/* The generalised winding number: inside tests that also answer for open and broken meshes.
+ * vertices (V,3) float32 finite, faces (F,3) int32 in [0, V), query (n,3) float32 finite: the kernels check none of
+ * it, the caller does.  0 <= F, 3 F < 2^31, 0 <= n < 2^31, 0 <= B <= F, lo / inv / dims as for the face grid above,
+ * else NERF_E_ARG; 64-bit arrays (keys, starts, moments, w) 8-byte aligned, else NERF_E_ALIGN; both before any
+ * launch.  Everything but the centroid cell is double, every operation rounded once ((x x' + y y') + z z' for a dot
+ * product, six products and three differences for a cross product).  No LDS, no atomics, one writer per output.
+ * nerf_mesh_winding_keys: keys[f] = (brick << 32) | f, brick the cell_id of the cell of the fp32 centroid
+ *   g_k = ((a_k + b_k) + c_k) * 0x1.555556p-2f of face f (the fp32 cell index of the face grid).  One thread per face.
+ * nerf_mesh_winding_soup: soup (F,9) float32, row j = the corners a, b, c of face sorted_keys[j] & 0xffffffff.
+ * nerf_mesh_winding_moments: starts (B,) int64 ascending with starts[0] = 0, the first sorted position of every
+ *   occupied brick; brick b owns [starts[b], starts[b+1]) ([.., F) for the last).  runs (B,2) int32 = that run;
+ *   moments (B,7) double = p (3), n (3), r2, summed over the run in sorted order by one thread: x = (b - a) x (c - a),
+ *   n += 0.5 x, m = sqrt(x . x), s = (a + b) + c, P += m s, M += m, S += s; p = P / (3 M) if M > 0 else
+ *   S / (3 count); r2 = the largest (corner - p) . (corner - p) of the run.
+ * nerf_mesh_winding: w[i] (double) = acc / 12.566370614359172, acc summed over the bricks b = 0 .. B-1 in order: with
+ *   d = p_b - q and d2 = d . d, brick b is far iff exact == 0 and d2 > (beta beta) r2_b (strict), and adds
+ *   (d . n_b) / (d2 sqrt(d2)); otherwise it adds 2 atan2(N, D) for the faces of its run in order, with a, b, c =
+ *   corner - q, N = a . (b x c), D = (((|a| |b|) |c| + (a . b) |c|) + (b . c) |a|) + (c . a) |b|, |a| = sqrt(a . a).
+ *   +1 inside a closed mesh whose normals point outwards.  beta finite and >= 1, exact in {0, 1}, (B > 0) == (F > 0),
+ *   else NERF_E_ARG.  B = 0: zeros.  One thread per query. */
+int nerf_mesh_winding_keys(const float* vertices, const int32_t* faces, int64_t F, const float* lo, float inv,
+                           const int32_t* dims, int64_t* keys, hipStream_t stream);
+int nerf_mesh_winding_soup(const float* vertices, const int32_t* faces, int64_t F, const int64_t* sorted_keys,
+                           float* soup, hipStream_t stream);
+int nerf_mesh_winding_moments(const float* soup, int64_t F, const int64_t* starts, int64_t B, int32_t* runs,
+                              double* moments, hipStream_t stream);
+int nerf_mesh_winding(const float* query, int64_t n, const int32_t* runs, const double* moments, int64_t B,
+                      const float* soup, int64_t F, double beta, int exact, double* w, hipStream_t stream);
+
 /* TSDF fusion of depth views.  The volume is the lattice of nerf_mesh_emit: tsdf and weight
  * (nx,ny,nz) contiguous fp32, p = (ix ny + iy) nz + iz, the point x = lo + (ix,iy,iz) h, h = (hi - lo) / (n - 1);
  * every dimension >= 2 and nx ny nz < 2^31, lo / hi HOST arrays of 3 floats with lo < hi (else NERF_E_ARG).  A fresh

@@ -176,6 +176,10 @@ def lib():
             "nerf_mesh_ray_cast": [P, I64, P, I64, P, P, I64, P, F, F, P, D, I, P, P, P, P],
             "nerf_mesh_point_crossings": [P, I64, P, I64, P, P, I64, P, F, F, P, P, P, P],
             "nerf_box_points": [I64, U64, P, P, P, P],
+            "nerf_mesh_winding_keys": [P, P, I64, P, F, P, P, P],
+            "nerf_mesh_winding_soup": [P, P, I64, P, P, P],
+            "nerf_mesh_winding_moments": [P, I64, P, I64, P, P, P],
+            "nerf_mesh_winding": [P, I64, P, P, I64, P, I64, D, I, P, P],
             "nerf_tsdf_integrate": [P, P, I, I, I, P, P, P, P, I, I, I, F, F, F, F, F, P],
             "nerf_tsdf_face_observed": [P, P, I, I, I, F, I64, P, P],
             "nerf_tsdf_integrate_color": [P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, F, F, F, P],
@@ -248,6 +252,7 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_face_areas", "nerf_mesh_sample_surface", "nerf_points_cell_keys", "nerf_points_nearest",
            "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces",
            "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points",
+           "nerf_mesh_winding_keys", "nerf_mesh_winding_soup", "nerf_mesh_winding_moments", "nerf_mesh_winding",
            "nerf_tsdf_integrate", "nerf_tsdf_face_observed", "nerf_tsdf_integrate_color", "nerf_tsdf_sample_color")
 
 

@@ -1091,11 +1091,12 @@ def _finite_box(points, what):
     return box
 
 
-def _grid_from_box(box, count, cell_size, what):
+def _grid_from_box(box, count, cell_size, what, per_axis=None):
     """The grid (lo, cell, inv, dims) of ``count`` items in ``box`` (of _finite_box; None for no items: one cell at the
     origin): lo 3 floats, cell and inv fp32 values as floats, dims 3 ints.  ``cell_size`` None: the default cell,
     longest extent / clamp(ceil(sqrt(count) / 2), 1, 1024), 1 for an all-zero extent; otherwise the caller has passed
-    it through _cell_size_arg already."""
+    it through _cell_size_arg already.  ``per_axis`` (with cell_size None): that many cells along the longest extent
+    instead of the square-root rule, an int in [1, 1024]."""
     import math
 
     import numpy as np
@@ -1108,14 +1109,15 @@ def _grid_from_box(box, count, cell_size, what):
         if not np.isfinite(ext).all():
             raise ValueError(f"the extent of the {what} overflows float32")
         if cell_size is None:
-            k = min(max(math.ceil(math.sqrt(count) / 2.0), 1), MAX_GRID_DIM)
+            k = min(max(math.ceil(math.sqrt(count) / 2.0), 1), MAX_GRID_DIM) if per_axis is None else per_axis
             cell = ext.max() / np.float32(k) if ext.max() > 0 else np.float32(1.0)
             inv = np.float32(1.0) / cell
             if not (np.isfinite(cell) and cell > 0 and np.isfinite(inv) and inv > 0):
                 cell, inv = np.float32(1.0), np.float32(1.0)  # an extent too small to divide: one cell holds it all
         cells = np.floor(ext * inv)  # fp32, like the kernel's cell index of the largest coordinate
     if cell_size is None:
-        cells = np.minimum(cells, MAX_GRID_DIM - 1)  # only rounding can exceed it; the kernel clamps into the last cell
+        # only rounding can exceed it; the kernel clamps into the last cell (with per_axis: the maximum itself too)
+        cells = np.minimum(cells, (MAX_GRID_DIM if per_axis is None else per_axis) - 1)
     elif not np.isfinite(cells).all() or cells.max() + 1 > MAX_GRID_DIM:
         raise ValueError(f"cell_size {cell_size!r} needs more than {MAX_GRID_DIM} cells along an axis")
     return lo.tolist(), float(cell), float(inv), [int(c) + 1 for c in cells]
@@ -1415,6 +1417,137 @@ def box_points(n, lo, hi, seed=0, device=None):
                                         (ctypes.c_float * 3)(*box[1].tolist()), ptr(points), stream()),
                   "nerf_box_points")
     return points
+
+
+# ------------------------------------------------------------------ generalised winding number
+
+
+_WINDING_KEYS = {"keys", "runs", "moments", "soup", "lo", "cell", "inv", "dims", "B", "F"}
+
+
+def _bricks_per_axis(F):
+    """the default: clamp(ceil(1.25 F^(1/4)), 1, 1024)"""
+    import math
+    return min(max(math.ceil(1.25 * F ** 0.25), 1), MAX_GRID_DIM)
+
+
+def mesh_winding_bricks(vertices, faces, bricks_per_axis=None):
+    """The bricks of the generalised winding number (nerf_mesh_winding_keys -> torch.sort -> nerf_mesh_winding_soup ->
+    nerf_mesh_winding_moments): vertices (V,3) float32, finite; faces (F,3) int32.  Every face belongs to ONE brick,
+    the cell of its fp32 centroid ((a + b) + c) * fp32(1/3) in a coarse grid over the box of ALL vertices (unlike
+    mesh_face_grid, which registers a face in every cell of its bounding box).  ``bricks_per_axis``: the cells along
+    the longest extent, an int in [1, 1024]; default clamp(ceil(1.25 F^(1/4)), 1, 1024).  cell = longest extent /
+    bricks_per_axis (1 for an all-zero extent), dims = min(floor((max - lo) * inv) + 1, bricks_per_axis) per axis in
+    fp32.  Returns the dict {keys (F,) int64 sorted, (brick << 32) | face; runs (B,2) int32, the sorted positions
+    [start, end) of every occupied brick; moments (B,7) float64, per brick the area-weighted centroid p (the plain
+    mean of the face centroids when the brick has no area), the dipole n = sum of 0.5 (b - a) x (c - a) and r2, the
+    largest squared distance from p to a corner of the brick; soup (F,9) float32, the corners in sorted order; lo (3
+    floats), cell, inv (fp32 values as floats), dims (3 ints), B, F}: 8 + 36 bytes per face and 64 per occupied brick.
+    The sums run in sorted order with one owner per brick: bitwise reproducible (and serial within a brick: a
+    bricks_per_axis far below the default makes the build slow on a large mesh).  F == 0 gives an empty grid (B = 0).
+    ValueError before any launch on CPU tensors, wrong dtypes or shapes, non-finite vertices, out-of-range indices and
+    a bad bricks_per_axis.  Host reads: the box (it carries the finiteness check), the index range, and the number of
+    occupied bricks."""
+    V = _vertices_arg(vertices)
+    _, F = _faces_arg(faces, V)
+    if bricks_per_axis is not None and (isinstance(bricks_per_axis, bool) or not isinstance(bricks_per_axis, int)
+                                        or not 1 <= bricks_per_axis <= MAX_GRID_DIM):
+        raise ValueError(f"bricks_per_axis must be an int in [1, {MAX_GRID_DIM}], got {bricks_per_axis!r}")
+    dev = vertices.device
+    box = _finite_box(vertices, "vertices") if V else None
+    k = _bricks_per_axis(F) if bricks_per_axis is None else bricks_per_axis
+    lo, cell, inv, dims = _grid_from_box(box if F else None, F, None, "vertices", per_axis=k)
+    bricks = {"lo": lo, "cell": cell, "inv": inv, "dims": dims, "B": 0, "F": F}
+    if F == 0:
+        bricks.update(keys=torch.empty(0, dtype=torch.int64, device=dev),
+                      runs=torch.empty((0, 2), dtype=torch.int32, device=dev),
+                      moments=torch.empty((0, 7), dtype=torch.float64, device=dev),
+                      soup=torch.empty((0, 9), dtype=F32, device=dev))
+        return bricks
+    lo_c, _, _, dims_c = _grid_c(bricks)
+    L = lib()
+    keys = torch.empty(F, dtype=torch.int64, device=dev)
+    check(L.nerf_mesh_winding_keys(ptr(vertices), ptr(faces), F, lo_c, inv, dims_c, ptr(keys), stream()),
+          "nerf_mesh_winding_keys")
+    keys = torch.sort(keys).values
+    soup = torch.empty((F, 9), dtype=F32, device=dev)
+    check(L.nerf_mesh_winding_soup(ptr(vertices), ptr(faces), F, ptr(keys), ptr(soup), stream()),
+          "nerf_mesh_winding_soup")
+    cells = keys >> 32
+    first = torch.ones(F, dtype=torch.bool, device=dev)
+    first[1:] = cells[1:] != cells[:-1]
+    starts = torch.nonzero(first).reshape(-1)  # (B,) int64 ascending, starts[0] = 0; the host read of B
+    B = int(starts.shape[0])
+    runs = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    moments = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    check(L.nerf_mesh_winding_moments(ptr(soup), F, ptr(starts), B, ptr(runs), ptr(moments), stream()),
+          "nerf_mesh_winding_moments")
+    bricks.update(keys=keys, runs=runs, moments=moments, soup=soup, B=B)
+    return bricks
+
+
+def _winding_bricks_arg(bricks, F):
+    """ValueError unless ``bricks`` is a dict of mesh_winding_bricks and belongs to F faces; returns B."""
+    if not isinstance(bricks, dict) or not _WINDING_KEYS <= set(bricks):
+        raise ValueError("bricks must be the dict that mesh_winding_bricks returns")
+    B = int(bricks["B"])
+    shapes = (("keys", torch.int64, (F,)), ("runs", torch.int32, (B, 2)), ("moments", torch.float64, (B, 7)),
+              ("soup", F32, (F, 9)))
+    if int(bricks["F"]) != F or not 0 <= B <= F or (F == 0) != (B == 0) or any(
+            not isinstance(bricks[name], torch.Tensor) or bricks[name].dtype != dtype
+            or tuple(bricks[name].shape) != shape for name, dtype, shape in shapes):
+        raise ValueError(f"bricks do not belong to these faces: bricks F = {bricks['F']}, B = {B}, F = {F}")
+    if F:
+        for name, dtype, _ in shapes:
+            need(bricks[name], f"bricks['{name}']", dtype)
+    return B
+
+
+def _beta_arg(beta):
+    import math
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not math.isfinite(beta) or beta < 1:
+        raise ValueError(f"beta must be a finite float >= 1, got {beta!r}")
+    return float(beta)
+
+
+def mesh_winding_number(query, vertices, faces, bricks, beta=3.0, exact=False, sort_queries=True,
+                        finite_checked=False):
+    """The generalised winding number of every query (nerf_mesh_winding): query (n,3) float32, finite; vertices and
+    faces the mesh that ``bricks`` = mesh_winding_bricks(vertices, faces) was built from.  Returns w (n,) float64:
+    (1 / 4 pi) times the sum over the faces of the signed solid angle 2 atan2(N, D) (Van Oosterom and Strackee) of the
+    face seen from the query.  On a closed mesh whose normals point outwards (positive Mesh.volume()) w is 1 inside
+    and 0 outside, the winding of mesh_point_crossings with the same sign; on an open or broken mesh it falls smoothly
+    from about 1 to about 0 across the holes, and "inside" is w > 0.5.  ``exact``: every face by its solid angle, in
+    sorted-face order, n x F of them.  Otherwise a brick with |p - q|^2 > beta^2 r2 (strictly) contributes its dipole
+    (p - q) . n / |p - q|^3 and only the nearer bricks are summed face by face; the error falls as beta grows (DESIGN
+    §3.11.10 has the table), beta a finite float >= 1.  One double accumulator per query, bricks in ascending key
+    order, faces in sorted order: bitwise reproducible, independent of the other queries.  ON the surface w is
+    whatever atan2(+-0, .) gives: deterministic, not meaningful.  ``sort_queries``: present the queries in the order
+    of their own cell keys in the brick grid (as points_nearest does); the result is the same either way.  A mesh
+    without faces gives zeros without a launch.  ValueError before any launch on CPU tensors, wrong dtypes or shapes,
+    non-finite queries or vertices, out-of-range indices, a bad beta, and bricks that are not the dict of these faces.
+    Host reads: the finiteness of the queries and of the vertices and the index range, all three skipped with
+    ``finite_checked``."""
+    beta = _beta_arg(beta)
+    n = _points_arg(query, "query") if finite_checked else _finite_points(query, "query")
+    V = _vertices_arg(vertices) if finite_checked else _finite_vertices(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=finite_checked)
+    B = _winding_bricks_arg(bricks, F)
+    dev = query.device
+    if F == 0 or n == 0:
+        return torch.zeros(n, dtype=torch.float64, device=dev)
+    w = torch.empty(n, dtype=torch.float64, device=dev)
+    L = lib()
+
+    def run(q, out_w):
+        check(L.nerf_mesh_winding(ptr(q), n, ptr(bricks["runs"]), ptr(bricks["moments"]), B, ptr(bricks["soup"]), F,
+                                  beta, int(bool(exact)), ptr(out_w), stream()), "nerf_mesh_winding")
+
+    if not sort_queries:
+        run(query, w)
+    else:
+        _run_sorted(query, n, _grid_c(bricks), (w,), run)
+    return w
 
 
 # ------------------------------------------------------------------ optimiser

@@ -355,18 +355,32 @@ class Mesh:
 
     # ---- containment on the device (kernels.mesh_point_crossings)
 
-    def contains(self, points, rule="parity", cell_size=None, grid=None):
+    def contains(self, points, rule="parity", cell_size=None, grid=None, beta=3.0, exact=False, bricks=None):
         """mesh_metrics.points_in_mesh(points, self, ...): (n,) bool, whether every row of ``points`` (n,3) float32 lies
         inside this mesh, by the parity of the faces the vertical ray from the point crosses (``rule`` = "winding":
-        by their winding number).  Exact except within rounding of the surface; meaningful for a closed mesh only."""
+        by their winding number).  Exact except within rounding of the surface; meaningful for a closed mesh only,
+        unless rule="generalized": winding_number(points, beta, exact, bricks) > 0.5, which answers for open and
+        broken meshes too."""
         from .mesh_metrics import points_in_mesh
-        return points_in_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid)
+        return points_in_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid, beta=beta, exact=exact,
+                              bricks=bricks)
 
-    def signed_distance(self, points, rule="parity", cell_size=None, grid=None):
+    def signed_distance(self, points, rule="parity", cell_size=None, grid=None, beta=3.0, exact=False, bricks=None):
         """mesh_metrics.signed_distance_to_mesh(points, self, ...): (sd (n,) float64, face (n,) int32, closest (n,3)
-        float32), the distance of closest_points with a negative sign inside; meaningful for a closed mesh only."""
+        float32), the distance of closest_points with a negative sign inside; meaningful for a closed mesh only,
+        unless rule="generalized" (the sign is then that of winding_number > 0.5)."""
         from .mesh_metrics import signed_distance_to_mesh
-        return signed_distance_to_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid)
+        return signed_distance_to_mesh(points, self, rule=rule, cell_size=cell_size, grid=grid, beta=beta, exact=exact,
+                                       bricks=bricks)
+
+    def winding_number(self, points, beta=3.0, exact=False, bricks=None):
+        """mesh_metrics.winding_number(points, self, ...): (n,) float64, the generalised winding number of every row of
+        ``points`` (n,3) float32: the signed solid angles of the faces over 4 pi, 1 inside and 0
+        outside a closed mesh wound outwards, a real number that falls smoothly across the holes of an open one.
+        ``exact``: every face; otherwise a dipole per brick of faces farther than ``beta`` brick radii.  ``bricks``: a
+        kernels.mesh_winding_bricks of this mesh built before.  ON the surface: deterministic, not meaningful."""
+        from .mesh_metrics import winding_number
+        return winding_number(points, self, beta=beta, exact=exact, bricks=bricks)
 
     def volume(self) -> float:
         """The signed volume: the float64 torch sum of a . (b x c) / 6 over the faces (the divergence theorem).
@@ -380,13 +394,16 @@ class Mesh:
         a, b, c = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
         return float((a * torch.linalg.cross(b, c)).sum() / 6.0)
 
-    def iou(self, other, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None) -> dict:
+    def iou(self, other, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None, beta=3.0, exact=False,
+            bricks=None) -> dict:
         """mesh_metrics.volume_iou(self, other, ...): the Monte Carlo volumetric intersection over union of two closed
-        meshes and the volumes it rests on, as a dict with self as a and other as b."""
+        meshes (open ones too with rule="generalized") and the volumes it rests on, as a dict with self as a and
+        other as b."""
         from .mesh_metrics import volume_iou
         if not isinstance(other, Mesh):
             raise ValueError(f"other must be a Mesh, got {type(other).__name__}")
-        return volume_iou(self, other, n_samples=n_samples, seed=seed, rule=rule, cell_size=cell_size)
+        return volume_iou(self, other, n_samples=n_samples, seed=seed, rule=rule, cell_size=cell_size, beta=beta,
+                          exact=exact, bricks=bricks)
 
     def render(self, H, W, fx, fy, cx, cy, c2w, near=0.0, far=float("inf"), cull_backfaces=False, grid=None) -> dict:
         """The mesh seen from a pinhole camera, through the rays of ray_sampling.rays_for_camera (pixel centres, the

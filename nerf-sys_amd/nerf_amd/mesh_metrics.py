@@ -21,7 +21,11 @@ for every ray, the nearest face it hits, the ray's parameter there and the baryc
 CONTAINMENT (csrc/mesh_inside.hip) is the third: points_in_mesh counts the faces the vertical ray from
 a query crosses, with an exact in-projection test, and from it come signed_distance_to_mesh (the sign for
 nearest_on_mesh's magnitude) and volume_iou (Monte Carlo over kernels.box_points).  All three mean something for a
-closed mesh only.
+closed mesh only, unless rule="generalized".
+
+THE GENERALISED WINDING NUMBER (csrc/mesh_winding.hip) answers for open and broken meshes too:
+winding_number sums the signed solid angles of the faces seen from a query, exactly or with a dipole per far brick of
+faces; rule="generalized" makes "inside" w > 0.5 in all three.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ import torch
 from . import kernels as K
 
 __all__ = ["nearest_points", "nearest_on_mesh", "ray_cast_mesh", "point_set_metrics", "mesh_distance",
-           "points_in_mesh", "signed_distance_to_mesh", "volume_iou"]
+           "points_in_mesh", "signed_distance_to_mesh", "volume_iou", "winding_number"]
 
 DEFAULT_SAMPLES = 2 ** 18
 
@@ -159,25 +163,57 @@ def ray_cast_mesh(rays, mesh, cell_size=None, cull_backfaces=False, grid=None):
 
 
 def _rule_arg(rule):
-    if rule not in ("parity", "winding"):
-        raise ValueError(f"rule must be 'parity' or 'winding', got {rule!r}")
+    if rule not in ("parity", "winding", "generalized"):
+        raise ValueError(f"rule must be 'parity', 'winding' or 'generalized', got {rule!r}")
     return rule
+
+
+def winding_number(query, mesh, beta=3.0, exact=False, bricks=None):
+    """(n,) float64: the generalised winding number of every row of ``query`` (n,3) float32 with respect to ``mesh`` (a
+    Mesh on the device): the sum of the signed solid angles of its faces over 4 pi (kernels.mesh_winding_number,
+    DESIGN §3.11.10).  1 inside and 0 outside a closed mesh whose normals point outwards; on an open or broken mesh a
+    real number that falls smoothly across the holes, "inside" being w > 0.5.  ``exact``: every face by its solid
+    angle; otherwise the bricks of faces farther than ``beta`` brick radii contribute a dipole each (the error falls
+    as beta grows).  ``bricks``: a kernels.mesh_winding_bricks of this mesh built before; default: built here.  ON the
+    surface the value is deterministic and not meaningful.  A mesh without faces gives zeros.  ValueError before any
+    launch as kernels.mesh_winding_bricks and kernels.mesh_winding_number state."""
+    K._beta_arg(beta)
+    if bricks is not None:
+        return K.mesh_winding_number(query, mesh.vertices, mesh.faces, bricks, beta=beta, exact=exact)
+    K._finite_points(query, "query")
+    bricks = K.mesh_winding_bricks(mesh.vertices, mesh.faces)  # it checks the mesh
+    return K.mesh_winding_number(query, mesh.vertices, mesh.faces, bricks, beta=beta, exact=exact, finite_checked=True)
+
+
+def _generalized_args(rule, beta, exact, bricks):
+    """beta, exact and bricks go with rule="generalized" alone: ValueError when one is set under another rule"""
+    _rule_arg(rule)
+    K._beta_arg(beta)
+    if rule != "generalized" and (beta != 3.0 or exact or bricks is not None):
+        raise ValueError("beta, exact and bricks go with rule='generalized' only")
 
 
 def _inside(crossings, winding, rule):
     return (crossings & 1).to(torch.bool) if rule == "parity" else winding != 0
 
 
-def points_in_mesh(query, mesh, rule="parity", cell_size=None, grid=None):
+def points_in_mesh(query, mesh, rule="parity", cell_size=None, grid=None, beta=3.0, exact=False, bricks=None):
     """(n,) bool: whether every row of ``query`` (n,3) float32 lies inside ``mesh`` (a Mesh on the device), from the
     faces the vertical ray from the query crosses (kernels.mesh_point_crossings).  ``rule``: "parity",
     an odd number of crossings, or "winding", a non-zero sum of the crossed faces' orientations (it tells a doubly
     covered region from an empty one; for a closed mesh without self-intersections both agree).  The answer means
-    something for a CLOSED mesh only; an extracted surface is open where it meets its box.  Exact except within
-    rounding of the surface itself.  ``grid``: a kernels.mesh_face_grid of this mesh built before (``cell_size`` is then
+    something for a CLOSED mesh only, unless rule="generalized"; an extracted surface is open where it meets its box.
+    rule="generalized": winding_number(query, mesh, beta, exact, bricks) > 0.5, which also answers for an open or
+    broken mesh; it uses no face grid, so a ``grid`` given with it is a ValueError, and ``beta``, ``exact`` and
+    ``bricks`` go with this rule alone.  Exact except within rounding of the surface itself.  ``grid``: a
+    kernels.mesh_face_grid of this mesh built before (``cell_size`` is then
     ignored); default: built here with ``cell_size``.  A mesh without faces contains nothing.  ValueError before any
     launch on a bad rule and as kernels.mesh_face_grid and kernels.mesh_point_crossings state."""
-    _rule_arg(rule)
+    _generalized_args(rule, beta, exact, bricks)
+    if rule == "generalized":
+        if grid is not None:
+            raise ValueError("rule='generalized' does not use a face grid: pass bricks, not grid")
+        return winding_number(query, mesh, beta=beta, exact=exact, bricks=bricks) > 0.5
     if grid is not None:
         return _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid), rule)
     K._finite_points(query, "query")
@@ -185,51 +221,79 @@ def points_in_mesh(query, mesh, rule="parity", cell_size=None, grid=None):
     return _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid, finite_checked=True), rule)
 
 
-def signed_distance_to_mesh(query, mesh, rule="parity", cell_size=None, grid=None):
+def signed_distance_to_mesh(query, mesh, rule="parity", cell_size=None, grid=None, beta=3.0, exact=False,
+                            bricks=None):
     """(sd (n,) float64, face (n,) int32, closest (n,3) float32): nearest_on_mesh's face and closest point, and the
     distance sqrt(d2) with the sign of points_in_mesh: negative inside, positive outside, +0.0 where d2 == 0.  One face
     grid serves both queries (``grid``: one built before; ``cell_size`` is then ignored).  The sign is that of a
-    CLOSED mesh (see points_in_mesh); no pseudo-normals are involved.  A mesh without faces gives +inf, -1 and the
-    query itself.  ValueError before any launch as points_in_mesh."""
-    _rule_arg(rule)
+    CLOSED mesh (see points_in_mesh), unless rule="generalized": the distance still comes through the face grid, the
+    sign from winding_number(query, mesh, beta, exact, bricks) > 0.5.  No pseudo-normals are involved.  A mesh without
+    faces gives +inf, -1 and the query itself.  ValueError before any launch as points_in_mesh."""
+    _generalized_args(rule, beta, exact, bricks)
     checked = grid is None
     if checked:
         K._finite_points(query, "query")
         grid = K.mesh_face_grid(mesh.vertices, mesh.faces, cell_size)  # it checks the mesh
+    if rule == "generalized" and bricks is not None:  # before the first query launch
+        K._winding_bricks_arg(bricks, int(mesh.faces.shape[0]))
     d2, face, closest = K.mesh_nearest_faces(query, mesh.vertices, mesh.faces, grid, finite_checked=checked)
-    inside = _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid, finite_checked=True), rule)
+    if rule == "generalized":
+        if bricks is None:
+            bricks = K.mesh_winding_bricks(mesh.vertices, mesh.faces)
+        inside = K.mesh_winding_number(query, mesh.vertices, mesh.faces, bricks, beta=beta, exact=exact,
+                                       finite_checked=True) > 0.5
+    else:
+        inside = _inside(*K.mesh_point_crossings(query, mesh.vertices, mesh.faces, grid, finite_checked=True), rule)
     d = torch.sqrt(d2)
     return torch.where(inside & (d2 > 0), -d, d), face, closest
 
 
-def volume_iou(mesh_a, mesh_b, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None):
-    """The volumetric intersection over union of two CLOSED meshes by Monte Carlo: ``n_samples`` kernels.box_points of
+def volume_iou(mesh_a, mesh_b, n_samples=2 ** 20, seed=0, rule="parity", cell_size=None, beta=3.0, exact=False,
+               bricks=None):
+    """The volumetric intersection over union of two CLOSED meshes (unless rule="generalized") by Monte Carlo:
+    ``n_samples`` kernels.box_points of
     the common box of both meshes' vertices, each tested with points_in_mesh against either mesh.  Returns a dict:
     iou = intersection / union (0.0 when the union is empty); volume_a, volume_b, intersection, union = the count
     times box volume / n_samples; count_a, count_b, count_intersection, count_union the four raw counts; n_samples; box
     = (lo, hi), the fp32 corners as lists.  The standard error of a volume is box volume sqrt(p (1 - p) / n_samples)
     for its share p.  Equal arguments give equal dicts (the points and the counts are bitwise reproducible).  Host
-    reads: the checks of both meshes, the two grids', the box, and one for the four counts.  ValueError before any launch on n_samples < 1, a bad
+    reads: the checks of both meshes, the two grids', the box, and one for the four counts.  rule="generalized": a
+    point is inside a mesh where its winding_number is above 0.5, which also answers for open meshes such as a TSDF
+    surface; ``beta`` and ``exact`` as there, ``bricks`` a pair (bricks of a, bricks of b) built before, and no face
+    grid is built.  ValueError before any launch on n_samples < 1, a bad
     seed or rule, a mesh without faces, and as kernels.mesh_face_grid states."""
     K._count_arg(n_samples, "n_samples")
     if n_samples < 1:
         raise ValueError(f"n_samples must be >= 1, got {n_samples!r}")
     K._seed_arg(seed)
-    _rule_arg(rule)
+    _generalized_args(rule, beta, exact, bricks)
     if cell_size is not None:
         K._cell_size_arg(cell_size)
+    if bricks is not None and (not isinstance(bricks, (tuple, list)) or len(bricks) != 2):
+        raise ValueError("bricks must be a pair: the mesh_winding_bricks of mesh_a and of mesh_b")
     for m in (mesh_a, mesh_b):  # both meshes before the first grid's launches
         K._faces_arg(m.faces, K._finite_vertices(m.vertices))
         if m.faces.shape[0] == 0:
             raise ValueError("volume_iou needs meshes with faces")
-    grid_a = K.mesh_face_grid(mesh_a.vertices, mesh_a.faces, cell_size)
-    grid_b = K.mesh_face_grid(mesh_b.vertices, mesh_b.faces, cell_size)
+    if rule == "generalized":
+        if bricks is None:
+            bricks = (K.mesh_winding_bricks(mesh_a.vertices, mesh_a.faces),
+                      K.mesh_winding_bricks(mesh_b.vertices, mesh_b.faces))
+        for m, b in zip((mesh_a, mesh_b), bricks):
+            K._winding_bricks_arg(b, int(m.faces.shape[0]))
+    else:
+        grid_a = K.mesh_face_grid(mesh_a.vertices, mesh_a.faces, cell_size)
+        grid_b = K.mesh_face_grid(mesh_b.vertices, mesh_b.faces, cell_size)
     both = torch.cat([mesh_a.vertices, mesh_b.vertices])
     box = torch.cat([both.amin(0), both.amax(0)]).tolist()
     lo, hi = box[:3], box[3:]
     points = K.box_points(n_samples, lo, hi, seed=seed, device=mesh_a.vertices.device)
-    ia = _inside(*K.mesh_point_crossings(points, mesh_a.vertices, mesh_a.faces, grid_a, finite_checked=True), rule)
-    ib = _inside(*K.mesh_point_crossings(points, mesh_b.vertices, mesh_b.faces, grid_b, finite_checked=True), rule)
+    if rule == "generalized":
+        ia, ib = (K.mesh_winding_number(points, m.vertices, m.faces, b, beta=beta, exact=exact,
+                                        finite_checked=True) > 0.5 for m, b in zip((mesh_a, mesh_b), bricks))
+    else:
+        ia = _inside(*K.mesh_point_crossings(points, mesh_a.vertices, mesh_a.faces, grid_a, finite_checked=True), rule)
+        ib = _inside(*K.mesh_point_crossings(points, mesh_b.vertices, mesh_b.faces, grid_b, finite_checked=True), rule)
     counts = torch.stack([ia.sum(), ib.sum(), (ia & ib).sum(), (ia | ib).sum()]).tolist()  # one host read
     scale = ((hi[0] - lo[0]) * (hi[1] - lo[1])) * (hi[2] - lo[2]) / n_samples
     out = dict(zip(("volume_a", "volume_b", "intersection", "union"), (c * scale for c in counts)))

@@ -46,7 +46,9 @@ no floor at the sampling spacing) and the line carries "exact": true; without it
 pair as --report-error, the exported mesh (a) and the surface before --simplify / --smooth (b): Mesh.iou (DESIGN
 §3.11.7), the Monte Carlo volumetric intersection over union from --iou-samples points of their common box, and both
 Mesh.volume() values.  All of it means something where the surfaces are closed; a surface that meets the box of the
-extraction is open there.
+extraction is open there.  --iou-rule generalized (default parity; the line then carries "rule") calls a point inside
+where the generalised winding number is above 0.5, which also answers for open surfaces: use it
+with --tsdf, whose meshes are open at every silhouette and unseen region.
 
   python tools/export_mesh.py --train-steps 2000 --keep-largest 1 --simplify 0.02 --report-iou --out mesh.ply
 
@@ -123,6 +125,9 @@ def main():
     ap.add_argument("--report-iou", action="store_true",
                     help="also print the volumetric IoU of the exported mesh and the surface before --simplify / --smooth")
     ap.add_argument("--iou-samples", type=int, default=2 ** 20, help="points of the common box for --report-iou")
+    ap.add_argument("--iou-rule", default="parity", choices=["parity", "winding", "generalized"],
+                    help="what --report-iou calls inside: crossing parity, crossing winding, or the generalised "
+                         "winding number above 0.5; use generalized with --tsdf, whose surfaces are open")
     ap.add_argument("--report-depth", type=int, default=0, metavar="VIEWS",
                     help="also compare the exported mesh's depth with the field's from this many cameras")
     ap.add_argument("--tsdf", type=int, default=0, metavar="VIEWS",
@@ -218,7 +223,8 @@ def main():
         else:
             print(json.dumps({"report_iou": {"a": "exported", "b": "before simplify / smooth",
                                              "mesh_volume_a": mesh.volume(), "mesh_volume_b": before.volume(),
-                                             **mesh.iou(before, n_samples=a.iou_samples)}}))
+                                             **({"rule": a.iou_rule} if a.iou_rule != "parity" else {}),
+                                             **mesh.iou(before, n_samples=a.iou_samples, rule=a.iou_rule)}}))
     if a.report_depth:
         print(json.dumps({"report_depth": depth_report(model, mesh, a.report_depth, a.image_size, a.samples)}))
 
