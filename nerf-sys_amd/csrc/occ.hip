@@ -475,6 +475,18 @@ __global__ void occ_update_kernel(float* __restrict__ occs, const int32_t* __res
   if (o >= 0.f) occs[id] = fmaxf(o * decay, val[i]);
 }
 
+// A draw in [0, range) from the counter RNG.  Up to 2^24 the 24-bit uniform times the range, truncated (the draws
+// every grid of R <= 256 has always had); above that the uniform would leave most of the range unreachable (at
+// range = 2^27 only multiples of 8), so the draw is the high half of the 64-bit mix times the range.
+__device__ __forceinline__ int64_t draw_below(uint64_t seed, uint64_t a, uint64_t b, int64_t range) {
+  if (range <= (int64_t)1 << 24) {
+    const uint64_t r = (uint64_t)(nerf_uniform(seed, a, b) * (float)range);
+    return (int64_t)(r < (uint64_t)range ? r : range - 1);
+  }
+  const uint64_t z = nerf_mix64(seed * 0x9e3779b97f4a7c15ULL + nerf_mix64(a * 0xd1b54a32d192ed03ULL + b));
+  return (int64_t)__umul64hi(z, (uint64_t)range);
+}
+
 // _sample_uniform_and_occupied_cells without a host read: per level l, n uniform cells, then n slots over the
 // level's occupied cells occ_list[pos[l*cpl] .. pos[(l+1)*cpl]) (count c on the device): every occupied cell
 // when c <= n (remaining slots -1 = empty), else n draws with replacement.  cells: L x 2n global cell ids.
@@ -485,8 +497,7 @@ __global__ void sample_cells_kernel(const int32_t* __restrict__ occ_list, const 
   const int l = (int)(i / (2 * n));
   const int64_t j = i - (int64_t)l * 2 * n;
   if (j < n) {
-    const uint64_t r = (uint64_t)(nerf_uniform(seed, 0x51u + (uint64_t)l, (uint64_t)j) * (float)cpl);
-    cells[i] = (int32_t)((int64_t)l * cpl + (int64_t)(r < (uint64_t)cpl ? r : cpl - 1));
+    cells[i] = (int32_t)((int64_t)l * cpl + draw_below(seed, 0x51u + (uint64_t)l, (uint64_t)j, cpl));
     return;
   }
   const int64_t k = j - n;
@@ -494,8 +505,7 @@ __global__ void sample_cells_kernel(const int32_t* __restrict__ occ_list, const 
   if (c <= n) {
     cells[i] = k < c ? occ_list[base + k] : -1;
   } else {
-    const uint64_t r = (uint64_t)(nerf_uniform(seed, 0xA3u + (uint64_t)l, (uint64_t)k) * (float)c);
-    cells[i] = occ_list[base + (int64_t)(r < (uint64_t)c ? r : c - 1)];
+    cells[i] = occ_list[base + draw_below(seed, 0xA3u + (uint64_t)l, (uint64_t)k, c)];
   }
 }
 
