@@ -37,14 +37,16 @@ extern "C" {
  * Pixel p of the batch is (img, row, col) = pix[3p..3p+2] (pix may be NULL: dense H*W image of
  * pose 0, row-major).  c2w: n_poses x 3 x 4 row-major.  aabb (6 floats min,max) or NULL for the
  * constant [near,far].  Writes rays (n,8) = [o, d, near, far].  If images_u8 != NULL (n_poses x H x
- * W x 3 bytes) the gathered pixel colour /255 is written to rgb_out (n,3). */
+ * W x 3 bytes) the gathered pixel colour /255 is written to rgb_out (n,3).  A NaN in the pose reaches near and far
+ * of the AABB test as NaN, as in the reference (torch's amax / clamp), so nerf_clamp_near_far calls the ray invalid. */
 int nerf_rays_gen(const float* c2w, int n_poses, const int32_t* pix, int64_t n, int H, int W,
                   float fx, float fy, float cx, float cy, int center_pixels, float near_v, float far_v,
                   const float* aabb, float aabb_max_bound, float aabb_invalid,
                   const uint8_t* images_u8, float* rays_out, float* rgb_out, hipStream_t stream);
 
 /* Random training batch: draws n (img,row,col) triplets with a counter-based RNG (seed) into
- * pix_out (n,3) — the data path of RamRaysDataset/DataLoader (pipelines/online_stage/runtime_adapt.py:76-86). */
+ * pix_out (n,3) — the data path of RamRaysDataset/DataLoader (pipelines/online_stage/runtime_adapt.py:76-86).
+ * n == 0 is an empty call (here and in nerf_pick_pixels_dseed): pix_out may be NULL. */
 int nerf_pick_pixels(int64_t n, int n_images, int H, int W, uint64_t seed, int32_t* pix_out,
                      hipStream_t stream);
 
@@ -55,7 +57,8 @@ int nerf_pick_pixels_dseed(int64_t n, int n_images, int H, int W, uint64_t seed_
                            const int64_t* step_dev, int32_t* pix_out, hipStream_t stream);
 
 /* clamp_rays_near_far (nerfs/ray_sampling.py:139-176), in place; valid_out (n) bytes or NULL.
- * has_near/has_far select the overrides.  Here and in nerf_rays_ndc, nerf_sample_stratified, nerf_build_xd,
+ * has_near/has_far select the overrides; a NaN near or far stays NaN through them (torch.maximum / minimum), so the
+ * ray is invalid.  Here and in nerf_rays_ndc, nerf_sample_stratified, nerf_build_xd,
  * nerf_sample_pdf and nerf_freq_encode n == 0 is an empty call: the scalar arguments are still checked, the buffers
  * may be NULL. */
 int nerf_clamp_near_far(float* rays, int64_t n, int has_near, float near_v, int has_far, float far_v,

@@ -10,6 +10,11 @@
 
 namespace {
 
+// torch.maximum / torch.minimum (and amax, amin, clamp) of the reference give NaN when an operand is NaN; C's fmaxf /
+// fminf return the other operand, which turned a NaN pose into a valid ray. For other operands these are fmaxf / fminf.
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
+
 __device__ __forceinline__ void aabb_slab(const float o[3], const float d[3], const float* aabb, float max_bound,
                                           float invalid, float& tn, float& tf) {
   const float eps = 1e-8f;
@@ -21,12 +26,12 @@ __device__ __forceinline__ void aabb_slab(const float o[3], const float d[3], co
     const float inv = 1.0f / rd;
     const float t0 = (aabb[k] - o[k]) * inv;
     const float t1 = (aabb[3 + k] - o[k]) * inv;
-    tmin = fmaxf(tmin, fminf(t0, t1));
-    tmax = fminf(tmax, fmaxf(t0, t1));
+    tmin = max_nan(tmin, min_nan(t0, t1));
+    tmax = min_nan(tmax, max_nan(t0, t1));
   }
-  tmin = fminf(fmaxf(tmin, 0.f), max_bound);
-  tmax = fminf(fmaxf(tmax, 0.f), max_bound);
-  if (tmax <= tmin) { tmin = invalid; tmax = invalid; }
+  tmin = min_nan(max_nan(tmin, 0.f), max_bound);
+  tmax = min_nan(max_nan(tmax, 0.f), max_bound);
+  if (tmax <= tmin) { tmin = invalid; tmax = invalid; }  // a NaN ray keeps near = far = NaN: clamp_ray drops it
   tn = tmin;
   tf = tmax;
 }
@@ -50,11 +55,12 @@ __device__ __forceinline__ void make_ray(const float* M, int row, int col, float
   if (aabb) aabb_slab(o, d, aabb, max_bound, invalid, tn, tf);
 }
 
-// clamp_rays_near_far (nerfs/ray_sampling.py:139-176) of one ray; returns valid
+// clamp_rays_near_far (nerfs/ray_sampling.py:139-176) of one ray; returns valid. A NaN near or far stays NaN through
+// the override, so the ray is invalid.
 __device__ __forceinline__ bool clamp_ray(float& a, float& b, int has_near, float nv, int has_far, float fv, float eps,
                                           float invalid) {
-  if (has_near) a = fmaxf(a, nv);
-  if (has_far) b = fminf(b, fv);
+  if (has_near) a = max_nan(a, nv);
+  if (has_far) b = min_nan(b, fv);
   const bool ok = isfinite(a) && isfinite(b) && (b > a + eps);
   if (has_near || has_far) {
     a = ok ? a : invalid;
@@ -295,16 +301,18 @@ extern "C" int nerf_rays_gen(const float* c2w, int n_poses, const int32_t* pix, 
 
 extern "C" int nerf_pick_pixels(int64_t n, int n_images, int H, int W, uint64_t seed, int32_t* pix_out,
                                 hipStream_t stream) {
-  NERF_CHECK_ARG(pix_out && n >= 0 && n_images > 0 && H > 0 && W > 0);
-  if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(n >= 0 && n_images > 0 && H > 0 && W > 0);
+  if (n == 0) return NERF_OK;  // torch hands out NULL for an empty tensor
+  NERF_CHECK_ARG(pix_out);
   pick_pixels_kernel<<<blocks_for(n, 256), 256, 0, stream>>>(n, n_images, H, W, seed, nullptr, 0, pix_out);
   return nerf_launch_status();
 }
 
 extern "C" int nerf_pick_pixels_dseed(int64_t n, int n_images, int H, int W, uint64_t seed_base, uint64_t seed_mul,
                                       const int64_t* step_dev, int32_t* pix_out, hipStream_t stream) {
-  NERF_CHECK_ARG(pix_out && step_dev && n >= 0 && n_images > 0 && H > 0 && W > 0);
+  NERF_CHECK_ARG(step_dev && n >= 0 && n_images > 0 && H > 0 && W > 0);
   if (n == 0) return NERF_OK;
+  NERF_CHECK_ARG(pix_out);
   pick_pixels_kernel<<<blocks_for(n, 256), 256, 0, stream>>>(n, n_images, H, W, seed_base, step_dev, seed_mul, pix_out);
   return nerf_launch_status();
 }
