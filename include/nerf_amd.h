@@ -657,6 +657,51 @@ int nerf_mesh_emit(const float* field, int nx, int ny, int nz, float iso, const 
                    const uint8_t* edge_mask, const int32_t* vert_off, const int32_t* face_off, int64_t V, int64_t F,
                    float* verts, int32_t* faces, float* normals, hipStream_t stream);
 
+/* Dual contouring over the same lattice: field, the index p, inside iff field > iso, lo / hi (HOST
+ * arrays of 3 floats, lo < hi) and the bound 12 nx ny nz < 2^31 are those of nerf_mesh_classify / nerf_mesh_emit (else
+ * NERF_E_ARG; the field must be finite, the kernels do not check).  Point p owns the axis edges p -> p + e_a,
+ * a = 0,1,2, that stay inside the lattice; cell p is the cell whose low corner is p (none on a high border).
+ * nerf_mesh_dual_classify: edge_mask[p] = crossing bits of the owned edges (bit a), edge_count[p] = their number,
+ *   cell_flag[p] = 1 iff cell p exists and its 8 inside bits are mixed (an active cell: one vertex), face_count[p] =
+ *   2 x the interior crossing edges of p, an edge along a being interior iff 1 <= j_b <= n_b - 2 and
+ *   1 <= j_c <= n_c - 2 for the two other axes, so that its four cells exist (they are then active).
+ * edge_off / cell_off / face_off = nerf_exclusive_scan_i32 of the three counts (nx ny nz + 1 entries each), E / V / F
+ *   their totals.  Edge (p, a) has the index edge_off[p] + popcount(edge_mask[p] & ((1 << a) - 1)).
+ * nerf_mesh_dual_edges: the Hermite data of every crossing edge, ordered by (p, a).  points (E,3) = the vertex
+ *   nerf_mesh_emit puts on that edge, bit for bit; normals (E,3) or NULL = its grid normal -g / max(|g|, 1e-12);
+ *   keys (E) or NULL = 3 p + a.  E = 0 launches nothing.
+ * nerf_mesh_dual_cells: one vertex per active cell and two triangles per interior crossing edge.  points / normals are
+ *   plain inputs, (E,3) in the order above: the caller may replace what nerf_mesh_dual_edges wrote.
+ *   Vertex cell_off[p]: the cell's 12 edges in the order a = 0,1,2, (b,c) = ((a+1)%3, (a+2)%3), corner offsets
+ *   (ob,oc) = (0,0),(1,0),(0,1),(1,1) (owner p + ob e_b + oc e_c).  Every crossing edge's point goes to the cell's
+ *   centred coordinates in double, y_k = (x_k - pa_k) / h_k - 0.5 with pa_k = lo_k + (float)i_k h_k in fp32; xbar is
+ *   their sum in that order over their number.  placement 0 (mean, surface nets): x = xbar.  placement 1 (QEF): every
+ *   crossing edge adds the plane through y with the direction m_k = n_k h_k (covariant, so anisotropic spacing is
+ *   right; |m| == 0 adds nothing), unit weight; x = the minimiser closest to xbar along the eigen-directions above
+ *   tol x the largest eigenvalue (8 cyclic Jacobi sweeps, the solve of nerf_mesh_cluster_quadric); where it is not
+ *   finite or leaves [-0.5, 0.5]^3, x = xbar and fallback[v] = 1 (else 0; always 0 for placement 0).
+ *   verts[v] = pa_k + (float)(x_k + 0.5) h_k: a vertex stays in its cell.  vertex_normals (V,3) or NULL: the double
+ *   sum s of the cell's edge normals in order, (float)(s / max(|s|, 1e-12)).  fallback (V) uint8 or NULL.
+ *   Faces [face_off[p], face_off[p+1]): for a = 0,1,2, an interior crossing edge (p, a) gives the quad over the cells
+ *   k0 = p - e_b - e_c, k1 = p - e_c, k2 = p, k3 = p - e_b (counter-clockwise seen from +a), kept when p is inside (so
+ *   normals point towards lower values, as nerf_mesh_emit's do) and reversed to k0 k3 k2 k1 otherwise, split on the
+ *   fixed diagonal: (v0,v1,v2), (v0,v2,v3).  A crossing edge on the border of the box gives Hermite data but no quad:
+ *   the surface is open at the box.  A cell that two sheets cross still gets one vertex, so a noisy field can give
+ *   edges shared by more than two triangles.
+ *   normals must not be NULL for placement 1 or with vertex_normals; 0 < tol < 1 (else NERF_E_ARG); an unknown
+ *   placement, V > nx ny nz, F > 6 nx ny nz or F > 0 with V = 0: NERF_E_ARG.  V = 0 launches nothing.
+ * One thread per lattice point, no LDS, no atomics, one writer per output slot: equal inputs give equal bits. */
+int nerf_mesh_dual_classify(const float* field, int nx, int ny, int nz, float iso, uint8_t* edge_mask,
+                            int32_t* edge_count, int32_t* cell_flag, int32_t* face_count, hipStream_t stream);
+int nerf_mesh_dual_edges(const float* field, int nx, int ny, int nz, float iso, const float* lo, const float* hi,
+                         const uint8_t* edge_mask, const int32_t* edge_off, int64_t E, float* points, float* normals,
+                         int32_t* keys, hipStream_t stream);
+int nerf_mesh_dual_cells(const float* field, int nx, int ny, int nz, float iso, const float* lo, const float* hi,
+                         const uint8_t* edge_mask, const int32_t* edge_off, const int32_t* cell_off,
+                         const int32_t* face_off, const float* points, const float* normals, int placement, double tol,
+                         int64_t V, int64_t F, float* verts, int32_t* faces, float* vertex_normals, uint8_t* fallback,
+                         hipStream_t stream);
+
 /* Mesh clean-up.  faces (F,3) int32 with 0 <= index < V: ANY indexed triangle list (any vertex
  * order, duplicated faces, repeated indices, unused vertices).  The kernels do not check the indices; the caller does.
  * V < 2^31 and 3 F < 2^31 (else NERF_E_ARG).

@@ -76,6 +76,27 @@ NERF_MQ_HD void add_face(Quadric& q, const double a[3], const double b[3], const
   q.b2 = q.b2 + Ld * mz;
 }
 
+// One plane through the local point y with the direction m (any length): L = |m|, u = m / L, d = -(u . y);
+// A += u u^T, b += d u (unit weight: dual contouring's Hermite planes, mesh_dual_core.hpp).  A direction with
+// L == 0 (or a NaN) adds nothing.
+NERF_MQ_HD void add_plane(Quadric& q, const double m[3], const double y[3]) {
+  const double xx = m[0] * m[0], yy = m[1] * m[1], zz = m[2] * m[2];
+  const double L = sqrt((xx + yy) + zz);
+  if (!(L > 0.0)) return;
+  const double ux = m[0] / L, uy = m[1] / L, uz = m[2] / L;
+  const double dx = ux * y[0], dy = uy * y[1], dz = uz * y[2];
+  const double d = -((dx + dy) + dz);
+  q.a00 = q.a00 + ux * ux;
+  q.a01 = q.a01 + ux * uy;
+  q.a02 = q.a02 + ux * uz;
+  q.a11 = q.a11 + uy * uy;
+  q.a12 = q.a12 + uy * uz;
+  q.a22 = q.a22 + uz * uz;
+  q.b0 = q.b0 + d * ux;
+  q.b1 = q.b1 + d * uy;
+  q.b2 = q.b2 + d * uz;
+}
+
 // One Jacobi rotation of the pair (p, q); r is the third index.  apq == 0 leaves everything as it is.  theta * theta
 // may overflow to +inf: then t = +-0, c = 1, s = +-0 and the rotation is the identity.
 NERF_MQ_HD void rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,

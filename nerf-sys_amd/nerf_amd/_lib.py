@@ -151,6 +151,9 @@ def lib():
             "nerf_moe_blend_bwd": [P, I64, P, P, I, I, P, P, P, P, P],
             "nerf_mesh_classify": [P, I, I, I, F, P, P, P, P],
             "nerf_mesh_emit": [P, I, I, I, F, P, P, P, P, P, I64, I64, P, P, P, P],
+            "nerf_mesh_dual_classify": [P, I, I, I, F, P, P, P, P, P],
+            "nerf_mesh_dual_edges": [P, I, I, I, F, P, P, P, P, I64, P, P, P, P],
+            "nerf_mesh_dual_cells": [P, I, I, I, F, P, P, P, P, P, P, P, P, I, D, I64, I64, P, P, P, P, P],
             "nerf_mesh_components": [P, I64, I64, P, P, P, P],
             "nerf_mesh_mark_used": [P, P, P, I64, I64, P, P, P],
             "nerf_mesh_remap_faces": [P, P, P, P, I64, I64, P, P],
@@ -253,7 +256,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_face_cell_counts", "nerf_mesh_face_cell_keys", "nerf_mesh_nearest_faces",
            "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points",
            "nerf_mesh_winding_keys", "nerf_mesh_winding_soup", "nerf_mesh_winding_moments", "nerf_mesh_winding",
-           "nerf_tsdf_integrate", "nerf_tsdf_face_observed", "nerf_tsdf_integrate_color", "nerf_tsdf_sample_color")
+           "nerf_tsdf_integrate", "nerf_tsdf_face_observed", "nerf_tsdf_integrate_color", "nerf_tsdf_sample_color",
+           "nerf_mesh_dual_classify", "nerf_mesh_dual_edges", "nerf_mesh_dual_cells")
 
 
 def check(status: int, what: str) -> None:

@@ -364,6 +364,129 @@ def mesh_extract(field, iso, lo, hi, normals=False, face_offsets=False):
     return out + (foff,) if face_offsets else out
 
 
+# ------------------------------------------------------------------ dual contouring
+
+_DUAL_PLACEMENT = {"mean": 0, "qef": 1}
+
+
+class DualLattice:
+    """What mesh_dual_hermite found on a lattice and mesh_dual_vertices needs again: the field, iso and the box, the
+    crossing bits of every point's three axis edges (mask), the exclusive scans of the edge, cell and face counts
+    (nx ny nz + 1 entries each, int32) and their totals E, V, F."""
+    __slots__ = ("field", "iso", "lo", "hi", "mask", "edge_off", "cell_off", "face_off", "E", "V", "F")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _hermite_arg(t, name, E, dev):
+    need(t, name)
+    if tuple(t.shape) != (E, 3):
+        raise ValueError(f"{name} must be ({E},3), got {tuple(t.shape)}")
+    if t.device != dev:
+        raise ValueError(f"{name} must be on {dev}, got {t.device}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} must be finite")
+    return t
+
+
+def mesh_dual_hermite(field, iso, lo, hi, normals=True):
+    """The Hermite data of dual contouring (nerf_mesh_dual_classify -> three scans -> nerf_mesh_dual_edges): field, iso
+    and the box as mesh_extract takes them.  Returns (record, points, normals, keys): a DualLattice, and for the E
+    crossing axis edges of the lattice, ordered by (point, axis), the crossing point (E,3) float32 (the bits of
+    mesh_extract's vertex on that edge), with ``normals`` the unit grid normal (E,3) float32 (else None), and
+    keys (E,) int32 = 3 p + a.  Two host reads: the finiteness check and the three totals."""
+    from .occupancy import exclusive_scan
+    need(field, "field")
+    if field.dim() != 3:
+        raise ValueError(f"field must be (nx,ny,nz), got {tuple(field.shape)}")
+    nx, ny, nz = (int(n) for n in field.shape)
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"every lattice dimension must be >= 2, got {(nx, ny, nz)}")
+    lo, hi = _box3(lo, "lo"), _box3(hi, "hi")
+    if not all(a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"lo must be below hi on every axis, got {lo} vs {hi}")
+    dev, P = field.device, nx * ny * nz
+    if 12 * P >= 2 ** 31:  # the bound of mesh_extract, so that both methods take the same lattices
+        raise ValueError(f"lattice too large: 12 * {P} points reaches 2^31")
+    if not bool(torch.isfinite(field).all()):
+        raise ValueError("field must be finite")
+    mask = torch.empty(P, dtype=torch.uint8, device=dev)
+    ecnt, ccnt, fcnt = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))  # 16-byte aligned each
+    check(lib().nerf_mesh_dual_classify(ptr(field), nx, ny, nz, float(iso), ptr(mask), ptr(ecnt), ptr(ccnt), ptr(fcnt),
+                                        stream()), "nerf_mesh_dual_classify")
+    eoff, coff, foff = exclusive_scan(ecnt), exclusive_scan(ccnt), exclusive_scan(fcnt)
+    E, V, F = (int(v) for v in torch.stack([eoff[-1], coff[-1], foff[-1]]).tolist())
+    points = torch.empty((E, 3), dtype=F32, device=dev)
+    nrm = torch.empty((E, 3), dtype=F32, device=dev) if normals else None
+    keys = torch.empty(E, dtype=torch.int32, device=dev)
+    lo_c, hi_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*hi)
+    check(lib().nerf_mesh_dual_edges(ptr(field), nx, ny, nz, float(iso), lo_c, hi_c, ptr(mask), ptr(eoff), E,
+                                     ptr(points) if E else None, ptr(nrm) if normals and E else None,
+                                     ptr(keys) if E else None, stream()), "nerf_mesh_dual_edges")
+    rec = DualLattice(field=field, iso=float(iso), lo=lo, hi=hi, mask=mask, edge_off=eoff, cell_off=coff, face_off=foff,
+                      E=E, V=V, F=F)
+    return rec, points, nrm, keys
+
+
+def mesh_dual_vertices(record, points, normals=None, placement="qef", tol=1e-3, vertex_normals=False,
+                       return_fallback=False):
+    """The dual mesh of a lattice from Hermite data (nerf_mesh_dual_cells): ``record`` from mesh_dual_hermite, points
+    (E,3) and normals (E,3) float32, finite, in that call's order; they may be what it returned or a replacement
+    (refined crossings, normals of the field itself).  One vertex per sign-changing cell: placement "mean" is the mean
+    of the cell's crossing points (surface nets); "qef" minimises the plane quadric of the cell's points and normals,
+    starting at that mean, with eigenvalues below ``tol`` x the largest truncated (0 < tol < 1), and keeps the mean
+    where the minimiser leaves the cell.  One quad (two triangles) per crossing edge whose four cells exist, normals
+    towards lower values; the surface is open at the box.  Returns verts (V,3) float32, faces (F,3) int32, then with
+    ``vertex_normals`` the normalised sums of each cell's edge normals (V,3) float32, then with ``return_fallback``
+    fallback (V,) uint8, 1 where "qef" kept the mean.  "qef" and ``vertex_normals`` need ``normals``.  A cell that two
+    sheets cross still gets one vertex, so noisy fields can give edges shared by more than two triangles.  Bitwise
+    reproducible (no atomics)."""
+    if not isinstance(record, DualLattice):
+        raise ValueError("record must be the DualLattice that mesh_dual_hermite returned")
+    if placement not in _DUAL_PLACEMENT:
+        raise ValueError(f'placement must be "qef" or "mean", got {placement!r}')
+    tol = float(tol)
+    if not 0.0 < tol < 1.0:  # a NaN fails both
+        raise ValueError(f"tol must be in (0, 1), got {tol}")
+    if normals is None and (placement == "qef" or vertex_normals):
+        raise ValueError('placement="qef" and vertex_normals need the (E,3) normals')
+    field = record.field
+    dev = field.device
+    nx, ny, nz = (int(n) for n in field.shape)
+    E, V, F = record.E, record.V, record.F
+    _hermite_arg(points, "points", E, dev)
+    if normals is not None:
+        _hermite_arg(normals, "normals", E, dev)
+    verts = torch.empty((V, 3), dtype=F32, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    vnrm = torch.empty((V, 3), dtype=F32, device=dev) if vertex_normals else None
+    fb = torch.empty(V, dtype=torch.uint8, device=dev) if return_fallback else None
+    if V:
+        lo_c, hi_c = (ctypes.c_float * 3)(*record.lo), (ctypes.c_float * 3)(*record.hi)
+        check(lib().nerf_mesh_dual_cells(ptr(field), nx, ny, nz, record.iso, lo_c, hi_c, ptr(record.mask),
+                                         ptr(record.edge_off), ptr(record.cell_off), ptr(record.face_off), ptr(points),
+                                         ptr(normals), _DUAL_PLACEMENT[placement], tol, V, F, ptr(verts),
+                                         ptr(faces) if F else None, ptr(vnrm), ptr(fb), stream()),
+              "nerf_mesh_dual_cells")
+    out = (verts, faces)
+    if vertex_normals:
+        out += (vnrm,)
+    if return_fallback:
+        out += (fb,)
+    return out
+
+
+def mesh_extract_dual(field, iso, lo, hi, placement="qef", tol=1e-3, normals=False):
+    """Dual contouring with the lattice's own Hermite data: mesh_dual_hermite then mesh_dual_vertices with the grid
+    normals.  Returns verts (V,3) float32 and faces (F,3) int32, and with ``normals`` the cell normals (V,3)."""
+    if placement not in _DUAL_PLACEMENT:
+        raise ValueError(f'placement must be "qef" or "mean", got {placement!r}')
+    rec, points, nrm, _ = mesh_dual_hermite(field, iso, lo, hi, normals=True)
+    return mesh_dual_vertices(rec, points, nrm, placement=placement, tol=tol, vertex_normals=normals)
+
+
 # ------------------------------------------------------------------ TSDF fusion of depth views (DESIGN §3.11.8)
 
 

@@ -6,6 +6,12 @@ of InstantNGP.normals.  Marching tetrahedra emits roughly 2-3 times the triangle
 resolution, and a lattice value exactly on the threshold gives zero-area triangles; the extractor keeps both as they
 are, so its connectivity is always closed inside the box.
 
+extract_mesh(method="dual") extracts by dual contouring instead (csrc/mesh_dual.hip): one vertex per
+sign-changing cell, placed by the plane quadric of the cell's crossing points and normals so that it can sit on a crease
+or a corner of the level set, and one quad per sign-changing lattice edge, about a third of the triangles.  The crossing
+points can be refined by bisection and the normals can come from the field itself.  The surface is open at the box, and
+a cell that two sheets cross still gets one vertex, so a noisy field can give edges shared by more than two triangles.
+
 Clean-up on the device (csrc/mesh_clean.hip): Mesh.components labels the connected components,
 Mesh.filter_components keeps whole components by their number of faces (the small detached blobs of a trained density
 field go), Mesh.select_faces compacts to any subset of the faces; normals and colours ride along.
@@ -494,11 +500,53 @@ def density_lattice(density_fn: Callable, lo, hi, resolution: Union[int, Sequenc
     return out.view(nx, ny, nz)
 
 
+def _refine_crossings(density_fn, record, keys, steps):
+    """``steps`` bisection steps of every crossing point along its own lattice edge (torch ops only): the bracket
+    starts at the edge's two lattice points (from ``keys`` = 3 p + a), the midpoint replaces the end whose
+    ``> threshold`` bit it shares, and the result is the last bracket's midpoint: (E,3) float32, exactly on the edge."""
+    field = record.field
+    nx, ny, nz = (int(n) for n in field.shape)
+    dev = field.device
+    lo_t = torch.tensor(record.lo, dtype=torch.float32, device=dev)
+    h = (torch.tensor(record.hi, dtype=torch.float32, device=dev) - lo_t) / torch.tensor(
+        [nx - 1, ny - 1, nz - 1], dtype=torch.float32, device=dev)
+    k = keys.to(torch.int64)
+    p, a = torch.div(k, 3, rounding_mode="floor"), k % 3
+    r = torch.div(p, nz, rounding_mode="floor")
+    idx = torch.stack([torch.div(r, ny, rounding_mode="floor"), r % ny, p % nz], -1)
+    rows = torch.arange(k.numel(), device=dev)
+    pts = lo_t + idx.to(torch.float32) * h
+    A = pts[rows, a]
+    B = lo_t[a] + (idx[rows, a] + 1).to(torch.float32) * h[a]
+    inside_a = field.reshape(-1)[p] > record.iso
+    with torch.no_grad():
+        for _ in range(int(steps)):
+            mid = 0.5 * (A + B)
+            pts[rows, a] = mid
+            same = (density_fn(pts).reshape(-1).to(torch.float32) > record.iso) == inside_a
+            A, B = torch.where(same, mid, A), torch.where(same, B, mid)
+    pts[rows, a] = 0.5 * (A + B)
+    return pts
+
+
+def _extract_dual(density_fn, field, threshold, lo, hi, cell_normals, placement, tol, hermite, refine) -> "Mesh":
+    record, points, nrm, keys = K.mesh_dual_hermite(field, threshold, lo, hi, normals=(hermite == "grid"))
+    if refine and record.E:
+        points = _refine_crossings(density_fn, record, keys, refine)
+    if callable(hermite):
+        nrm = hermite(points) if record.E else torch.empty_like(points)
+        if not isinstance(nrm, torch.Tensor) or tuple(nrm.shape) != tuple(points.shape):
+            raise ValueError(f"hermite must return a tensor {tuple(points.shape)}")
+        nrm = nrm.detach().to(torch.float32).contiguous()
+    return Mesh(*K.mesh_dual_vertices(record, points, nrm, placement=placement, tol=tol, vertex_normals=cell_normals))
+
+
 def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[int]], threshold: float,
                  normals: Union[str, None, Callable] = "grid", chunk: int = 2 ** 20, device=None,
                  min_faces: Optional[int] = None, keep_largest: Optional[int] = None,
                  simplify: Optional[float] = None, smooth: Optional[int] = None,
-                 simplify_placement: str = "mean") -> Mesh:
+                 simplify_placement: str = "mean", method: str = "tets", placement: str = "qef", tol: float = 1e-3,
+                 hermite: Union[str, Callable] = "grid", refine: int = 0) -> Mesh:
     """The level set density_fn = threshold inside the box [lo, hi] as a Mesh on the device.  normals: "grid" (the
     lattice's central differences, from the extraction kernel), None, or a callable evaluated at the vertices
     ((V,3) -> (V,3)).  min_faces / keep_largest (at most one): Mesh.filter_components on the extracted surface, before
@@ -507,7 +555,20 @@ def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[i
     normals are averaged per cell by the clustering kernel.  simplify_placement: "mean" or "quadric", the ``placement``
     of Mesh.simplify (quadric-error vertices keep edges, corners and volume; faces and attributes are the same).
     smooth: a number of Taubin iterations for Mesh.smooth with its defaults, applied after ``simplify`` and also before a callable ``normals``; "grid" normals are then replaced
-    by the face-derived normals of the smoothed mesh (Mesh.compute_normals).  None returns the surface unsmoothed."""
+    by the face-derived normals of the smoothed mesh (Mesh.compute_normals).  None returns the surface unsmoothed.
+
+    method: "tets" (marching tetrahedra, kernels.mesh_extract: vertices on lattice edges, 2-3 times the triangles of
+    marching cubes) or "dual" (dual contouring, kernels.mesh_dual_hermite / mesh_dual_vertices, DESIGN §3.11.11: one
+    vertex per sign-changing cell and one quad per sign-changing lattice edge, about a third of the triangles, and
+    vertices that can sit on creases and corners of the level set).  The other options below are "dual"'s.
+    placement: "qef" (the vertex minimises the plane quadric of the cell's crossing points and normals; ``tol`` in
+    (0, 1) truncates its small eigenvalues as Mesh.simplify's does) or "mean" (surface nets).  hermite: "grid" (normals
+    of the lattice's central differences) or a callable (E,3) crossing points -> (E,3) normals, for a field that knows
+    its own gradient.  refine: bisection steps of every crossing point along its own lattice edge, each one call of
+    density_fn on (E,3) points, before a callable ``hermite`` is evaluated.  normals="grid" gives the normalised sum of
+    each cell's edge normals.  Every later option works on the result unchanged.  A cell that two sheets of the level
+    set cross still gets one vertex, so a noisy field can give edges shared by more than two triangles; the surface
+    is open at the box, as marching tetrahedra's is."""
     if not (normals is None or normals == "grid" or callable(normals)):
         raise ValueError(f"normals must be 'grid', None or a callable, got {normals!r}")
     if smooth is not None and (isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0):
@@ -516,9 +577,24 @@ def extract_mesh(density_fn: Callable, lo, hi, resolution: Union[int, Sequence[i
         raise ValueError("give at most one of min_faces and keep_largest")
     if simplify_placement not in ("mean", "quadric"):
         raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
+    if method not in ("tets", "dual"):
+        raise ValueError(f'method must be "tets" or "dual", got {method!r}')
+    if placement not in ("qef", "mean"):
+        raise ValueError(f'placement must be "qef" or "mean", got {placement!r}')
+    if not 0.0 < float(tol) < 1.0:
+        raise ValueError(f"tol must be in (0, 1), got {tol!r}")
+    if not (hermite == "grid" or callable(hermite)):
+        raise ValueError(f"hermite must be 'grid' or a callable, got {hermite!r}")
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or refine < 0:
+        raise ValueError(f"refine must be an int >= 0, got {refine!r}")
+    if method == "tets" and (callable(hermite) or refine):
+        raise ValueError('hermite and refine belong to method="dual"')
     lo, hi = _box(lo, hi)
     field = density_lattice(density_fn, lo, hi, resolution, chunk=chunk, device=device)
-    mesh = Mesh(*K.mesh_extract(field, threshold, lo, hi, normals=(normals == "grid")))
+    if method == "dual":
+        mesh = _extract_dual(density_fn, field, threshold, lo, hi, normals == "grid", placement, tol, hermite, refine)
+    else:
+        mesh = Mesh(*K.mesh_extract(field, threshold, lo, hi, normals=(normals == "grid")))
     if min_faces is not None or keep_largest is not None:
         mesh = mesh.filter_components(min_faces=min_faces, keep_largest=keep_largest)
     if simplify is not None:

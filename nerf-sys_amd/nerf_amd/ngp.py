@@ -795,7 +795,8 @@ class InstantNGP(nn.Module):
 
     def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
                      chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None, simplify=None,
-                     smooth=None, simplify_placement="mean"):
+                     smooth=None, simplify_placement="mean", method="tets", placement="qef", tol: float = 1e-3,
+                     hermite="field", refine: int = 0):
         """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
         (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
         (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
@@ -806,8 +807,19 @@ class InstantNGP(nn.Module):
         (vertex clustering), applied after that filter and likewise before field normals and colours.  smooth: a
         number of Taubin iterations for Mesh.smooth, applied after ``simplify``: field normals and colours are then
         evaluated at the smoothed vertices, and "grid" normals become the face-derived normals of the smoothed mesh.
-        simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify (quadric-error vertices)."""
+        simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify (quadric-error vertices).
+        method: "tets" or "dual" (dual contouring, mesh.extract_mesh); placement, tol and refine as there, for "dual"
+        only.  hermite: the normals of dual contouring's crossing points, "field" (self.normals there, one fused
+        launch) or "grid" (the lattice's central differences); marching tetrahedra does not use it."""
         from .mesh import extract_mesh
+        if method not in ("tets", "dual"):
+            raise ValueError(f'method must be "tets" or "dual", got {method!r}')
+        if hermite not in ("field", "grid"):
+            raise ValueError(f"hermite must be 'field' or 'grid', got {hermite!r}")
+        dual = {}
+        if method == "dual":
+            dual = dict(method="dual", placement=placement, tol=tol, refine=refine,
+                        hermite=(lambda x: self.normals(x, params)) if hermite == "field" else "grid")
         if simplify_placement not in ("mean", "quadric"):
             raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         if normals not in ("field", "grid", None):
@@ -820,7 +832,7 @@ class InstantNGP(nn.Module):
         mesh = extract_mesh(lambda x: self.density(x, params), box[:3], box[3:], resolution, threshold,
                             normals="grid" if normals == "grid" else None, chunk=chunk,
                             device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest,
-                            simplify=simplify, smooth=smooth, simplify_placement=simplify_placement)
+                            simplify=simplify, smooth=smooth, simplify_placement=simplify_placement, **dual)
         return self._mesh_attributes(mesh, normals, colors, params, chunk)
 
     def extract_mesh_tsdf(self, poses, H, W, fx, fy, cx, cy, near, far, resolution=256, aabb=None, trunc=None,

@@ -86,14 +86,18 @@ class TSDFVolume:
     def extract_mesh(self, min_weight=1, normals: Optional[str] = "grid", min_faces: Optional[int] = None,
                      keep_largest: Optional[int] = None, simplify: Optional[float] = None,
                      smooth: Optional[int] = None, colors: Optional[str] = None,
-                     simplify_placement: str = "mean") -> Mesh:
+                     simplify_placement: str = "mean", method: str = "tets") -> Mesh:
         """The zero level of the fused field as a Mesh: mesh_extract(-tsdf, 0) (inside is tsdf < 0, normals point to
         larger tsdf: outwards), then only the faces of cells whose 8 corners all have weight >= min_weight
         (min_weight = 0 keeps every face, the sheet at -trunc behind the surface included), then the options of
         mesh.extract_mesh in its order: min_faces / keep_largest (at most one), simplify, smooth.  colors: None, or
         "fused" on a volume with colour: sample_colors at the final vertices, after the filters, simplify and smooth,
         as Mesh.colors (0.5 where no view coloured a corner of the vertex's cell).  simplify_placement: "mean" or
-        "quadric", the ``placement`` of Mesh.simplify."""
+        "quadric", the ``placement`` of Mesh.simplify.  method: "tets" only; the observed-face filter maps a face to
+        the one cell that emitted it, and a quad of dual contouring spans four."""
+        if method != "tets":
+            raise ValueError(f'TSDFVolume.extract_mesh supports method="tets" only, got {method!r}: its observed-face '
+                             "filter needs one cell per face, and a dual-contouring quad spans four cells")
         if simplify_placement not in ("mean", "quadric"):
             raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         if normals not in ("grid", None):

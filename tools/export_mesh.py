@@ -74,6 +74,17 @@ colours every vertex from the volume instead of querying the c
 works for models without such a query.  The first JSON line then says "colors": "fused".
 
   python tools/export_mesh.py --train-steps 2000 --tsdf 32 --colors fused --out mesh.ply
+
+--method dual (default tets; the files and every JSON line are unchanged without it) extracts by dual contouring
+ instead of marching tetrahedra: one vertex per sign-changing cell, one quad per sign-changing lattice
+edge, about a third of the triangles.  --dual-placement qef|mean chooses the vertex (the minimum of the cell's plane
+quadric, or the mean of its crossing points), --dual-hermite field|grid the normals of the crossing points (the field's
+own gradient, or the lattice's central differences) and --dual-refine N bisects every crossing point N times along its
+lattice edge with the density itself.  Every option and report above works on the result; the first JSON line gains
+"method", "dual_placement", "dual_hermite" and "dual_refine".  Not with --tsdf, whose observed-face filter needs one
+cell per face.
+
+  python tools/export_mesh.py --train-steps 2000 --method dual --dual-refine 4 --report-depth 4 --out mesh.ply
 """
 import argparse
 import json
@@ -134,11 +145,23 @@ def main():
                     help="export the TSDF fusion of the depth of this many cameras instead of the density level set")
     ap.add_argument("--tsdf-min-weight", type=float, default=1.0,
                     help="--tsdf keeps the faces of cells whose corners were all updated by this many views")
+    ap.add_argument("--method", default="tets", choices=["tets", "dual"],
+                    help="marching tetrahedra, or dual contouring (one vertex per cell, one quad per crossing edge)")
+    ap.add_argument("--dual-placement", default="qef", choices=["qef", "mean"],
+                    help="--method dual: the quadric-error minimum of the cell's Hermite data, or the mean of its points")
+    ap.add_argument("--dual-hermite", default="field", choices=["field", "grid"],
+                    help="--method dual: normals of the crossing points from the field's gradient or the lattice's")
+    ap.add_argument("--dual-refine", type=int, default=0, metavar="N",
+                    help="--method dual: bisection steps of every crossing point along its lattice edge")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
     if a.colors == "fused" and not a.tsdf:
         ap.error("--colors fused needs --tsdf VIEWS: the colours are fused from the rendered views")
+    if a.method == "dual" and a.tsdf:
+        ap.error("--method dual does not combine with --tsdf: its observed-face filter needs one cell per face")
+    dual = dict(method="dual", placement=a.dual_placement, hermite=a.dual_hermite, refine=a.dual_refine) \
+        if a.method == "dual" else {}
     if not torch.cuda.is_available():
         raise SystemExit("export_mesh: needs a GPU (no CPU fallback)")
     from nerf_amd.ngp import InstantNGP
@@ -178,7 +201,7 @@ def main():
                                            ray_samples=a.samples, **kw)
     else:
         def extract(**kw):
-            return model.extract_mesh(resolution=a.resolution, threshold=a.threshold, **kw)
+            return model.extract_mesh(resolution=a.resolution, threshold=a.threshold, **dual, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mesh = extract(normals=None if a.normals == "none" else a.normals, colors=None if a.colors == "none" else a.colors,
@@ -204,7 +227,9 @@ def main():
                       "faces_after_simplify": int(mesh.faces.shape[0]) if a.simplify is not None else None,
                       "extract_seconds": round(dt, 4), "out": a.out,
                       **({"simplify_placement": a.simplify_placement} if a.simplify_placement != "mean" else {}),
-                      **({"tsdf": a.tsdf, "tsdf_min_weight": a.tsdf_min_weight} if a.tsdf else {})}))
+                      **({"tsdf": a.tsdf, "tsdf_min_weight": a.tsdf_min_weight} if a.tsdf else {}),
+                      **({"method": "dual", "dual_placement": a.dual_placement, "dual_hermite": a.dual_hermite,
+                          "dual_refine": a.dual_refine} if dual else {})}))
     if a.report_error:
         # the surface the clustering and the smoothing started from: extracted again, filtered, nothing else
         before = extract(normals=None, min_faces=a.min_faces, keep_largest=a.keep_largest)
