@@ -1017,6 +1017,32 @@ int nerf_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, 
 int nerf_tsdf_sample_color(const float* color, int nx, int ny, int nz, const float* lo, const float* hi,
                            const float* points, int64_t N, float* rgb_out, float* cover_out, hipStream_t stream);
 
+/* Texture baking for meshes.  The atlas is a function of (F, S = texels) alone: faces 2c and 2c + 1
+ * share the square cell c of S x S texels, cells = max(1, (F + 1) / 2), cols = the smallest integer with
+ * cols^2 >= cells, T = cols S, cell c starts at texel (S (c % cols), S (c / cols)); texel units, x right, y down.  In
+ * its cell the even face has the UV corners (1,1), (S-3,1), (1,S-3) for its vertices 0, 1, 2, the odd face
+ * (S-1,S-1), (3,S-1), (S-1,3); texel (i,j) of a cell belongs to the even face where i + j < S, else to the odd one,
+ * and to nobody where that face is >= F.  S >= 5, T <= 16384, 3 F < 2^31, and T as passed equal to cols S (else
+ * NERF_E_ARG).  Everything rounds once per operation.
+ * nerf_mesh_atlas_texels: one thread per texel p = j T + i.  face (T,T) int32, -1 for an unowned texel; bary (T,T,2) =
+ *   (b1, b2): with (x, y) the texel's centre inside its cell, turned back to (S - x, S - y) for an odd face, and
+ *   L = S - 4: b1 = max((x - 1) / L, 0), b2 = max((y - 1) / L, 0), both divided by their sum where it exceeds 1,
+ *   b0 = max((1 - b1) - b2, 0); position (T,T,3) = (b0 v0 + b1 v1) + b2 v2 in fp32; normal (T,T,3) or NULL: in double,
+ *   rounded to fp32 at the end, g / |g| with g = (b0 n0 + b1 n1) + b2 n2 of vertex_normals (V,3), or with
+ *   vertex_normals NULL g = (v1 - v0) x (v2 - v0); zeros where |g| = 0.  An unowned texel gets zeros.  F = 0 is legal
+ *   (T = S, nobody owns a texel).  vertex_normals without normal is NERF_E_ARG.  The vertex indices are not checked.
+ * nerf_mesh_texture_lookup: texture (T,T,C) fp32, 1 <= C <= 4; face (N) int32 and bary (N,2) = (u, v) as
+ *   nerf_mesh_ray_cast returns them; out (N,C).  In the face's cell (x, y) = (w0 P0 + u P1) + v P2 of its corners with
+ *   w0 = (1 - u) - v; i0 = floor(x - .5), fx = (x - .5) - i0, likewise j0, fy; the cell's origin is added to i0, i0 + 1,
+ *   j0, j0 + 1 and each is clamped to [0, T - 1]; top = c00 + fx (c10 - c00), bot = c01 + fx (c11 - c01),
+ *   out = top + fy (bot - top) per channel.  face < 0 gives zeros.  A face >= F or a pair outside the triangle reads
+ *   other texels, never outside the texture.  N = 0 launches nothing.  One thread per lookup. */
+int nerf_mesh_atlas_texels(const float* vertices, const int32_t* faces, int64_t F, int texels, int T,
+                           const float* vertex_normals, int32_t* face, float* bary, float* position, float* normal,
+                           hipStream_t stream);
+int nerf_mesh_texture_lookup(const float* texture, int T, int C, int64_t F, int texels, const int32_t* face,
+                             const float* bary, int64_t N, float* out, hipStream_t stream);
+
 /* Library build identification (string, static). */
 const char* nerf_version(void);
 

@@ -187,6 +187,8 @@ def lib():
             "nerf_tsdf_face_observed": [P, P, I, I, I, F, I64, P, P],
             "nerf_tsdf_integrate_color": [P, P, P, I, I, I, P, P, P, P, P, I, I, I, F, F, F, F, F, P],
             "nerf_tsdf_sample_color": [P, I, I, I, P, P, P, I64, P, P, P],
+            "nerf_mesh_atlas_texels": [P, P, I64, I, I, P, P, P, P, P, P],
+            "nerf_mesh_texture_lookup": [P, I, I, I64, I, P, P, I64, P, P],
         }
         ab = "NERF_AMD_LIB" in os.environ  # an A/B build of an older revision may lack the newer entry points
         for name, args in sig.items():
@@ -257,7 +259,8 @@ EXPORTS = ("nerf_rays_gen", "nerf_pick_pixels", "nerf_clamp_near_far", "nerf_ray
            "nerf_mesh_ray_cast", "nerf_mesh_point_crossings", "nerf_box_points",
            "nerf_mesh_winding_keys", "nerf_mesh_winding_soup", "nerf_mesh_winding_moments", "nerf_mesh_winding",
            "nerf_tsdf_integrate", "nerf_tsdf_face_observed", "nerf_tsdf_integrate_color", "nerf_tsdf_sample_color",
-           "nerf_mesh_dual_classify", "nerf_mesh_dual_edges", "nerf_mesh_dual_cells")
+           "nerf_mesh_dual_classify", "nerf_mesh_dual_edges", "nerf_mesh_dual_cells",
+           "nerf_mesh_atlas_texels", "nerf_mesh_texture_lookup")
 
 
 def check(status: int, what: str) -> None:

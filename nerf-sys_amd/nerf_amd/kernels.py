@@ -1673,6 +1673,112 @@ def mesh_winding_number(query, vertices, faces, bricks, beta=3.0, exact=False, s
     return w
 
 
+# ------------------------------------------------------------------ texture baking
+
+ATLAS_MIN_TEXELS = 5
+ATLAS_MAX_SIDE = 16384
+
+
+def atlas_layout(n_faces, texels):
+    """(cols, T) of the texture atlas of ``n_faces`` faces with cells of ``texels`` x ``texels`` texels: faces 2c and
+    2c + 1 share cell c, cells = max(1, (F + 1) // 2), cols = the smallest integer with cols^2 >= cells (integer
+    arithmetic), T = cols * texels; cell c starts at texel (texels * (c % cols), texels * (c // cols)).  ValueError on
+    ``texels`` that is no int >= 5, a negative face count and T > 16384."""
+    import math
+    if isinstance(texels, bool) or not isinstance(texels, int) or texels < ATLAS_MIN_TEXELS:
+        raise ValueError(f"texels must be an int >= {ATLAS_MIN_TEXELS}, got {texels!r}")
+    F = int(n_faces)
+    if F < 0:
+        raise ValueError(f"the face count must be >= 0, got {F}")
+    cells = max(1, (F + 1) // 2)
+    cols = math.isqrt(cells - 1) + 1
+    T = cols * texels
+    if T > ATLAS_MAX_SIDE:
+        raise ValueError(f"{F} faces at {texels} texels need a {T} x {T} texture: the limit is {ATLAS_MAX_SIDE}")
+    return cols, T
+
+
+def mesh_atlas_texels(vertices, faces, texels, vertex_normals=None, normals=True, ranges_checked=False):
+    """What every texel of the atlas of (F, texels) stands for (nerf_mesh_atlas_texels): vertices
+    (V,3) float32, faces (F,3) int32.  Returns a dict of (T,T,...) device tensors indexed [y, x]: "face" int32, the
+    owning face or -1; "bary" (T,T,2) float32, the pair (b1, b2) of the surface point; "position" (T,T,3) float32 =
+    b0 v0 + b1 v1 + b2 v2; with ``normals`` also "normal" (T,T,3) float32: the normalised mix of ``vertex_normals``
+    (V,3) with the same weights, or without them the face's unit normal by its winding, zeros where the length is
+    zero; and "texels", "cols", "T" as ints.  An unowned texel holds zeros.  A texel in the gutter of its face takes
+    a nearby boundary point of that face.  NaN vertices propagate; F = 0 gives a T = texels atlas that nobody owns.
+    Bitwise reproducible.  ValueError before the launch on CPU tensors, wrong dtypes or shapes, out-of-range indices
+    (one host read, skipped with ``ranges_checked``), texels < 5 and T > 16384."""
+    V = _vertices_arg(vertices)
+    _, F = _faces_arg(faces, V, ranges_checked=ranges_checked)
+    cols, T = atlas_layout(F, texels)
+    if faces.device != vertices.device:
+        raise ValueError("vertices and faces must be on one device")
+    if vertex_normals is not None:
+        if not normals:
+            raise ValueError("vertex_normals are given but normals are not asked for")
+        need(vertex_normals, "vertex_normals")
+        if tuple(vertex_normals.shape) != (V, 3) or vertex_normals.device != vertices.device:
+            raise ValueError(f"vertex_normals must be ({V},3) on the vertices' device, got {tuple(vertex_normals.shape)}")
+    dev = vertices.device
+    out = {"face": torch.empty((T, T), dtype=torch.int32, device=dev), "bary": torch.empty((T, T, 2), dtype=F32, device=dev),
+           "position": torch.empty((T, T, 3), dtype=F32, device=dev)}
+    if normals:
+        out["normal"] = torch.empty((T, T, 3), dtype=F32, device=dev)
+    check(lib().nerf_mesh_atlas_texels(ptr(vertices) if F else None, ptr(faces) if F else None, F, texels, T,
+                                       ptr(vertex_normals) if F else None, ptr(out["face"]), ptr(out["bary"]),
+                                       ptr(out["position"]), ptr(out.get("normal")), stream()),
+          "nerf_mesh_atlas_texels")
+    out.update(texels=texels, cols=cols, T=T)
+    return out
+
+
+def _texture_arg(texture, n_faces, texels):
+    """texture (T,T,C) float32 on the device, 1 <= C <= 4, T the side of the atlas of (n_faces, texels)."""
+    need(texture, "texture")
+    if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or not 1 <= texture.shape[2] <= 4:
+        raise ValueError(f"texture must be (T,T,C) with 1 <= C <= 4, got {tuple(texture.shape)}")
+    if isinstance(texels, bool) or not isinstance(texels, int) or texels < ATLAS_MIN_TEXELS:
+        raise ValueError(f"texels must be an int >= {ATLAS_MIN_TEXELS}, got {texels!r}")
+    side = int(texture.shape[0])
+    if side % texels:
+        raise ValueError(f"texels = {texels} does not divide the texture's side {side}")
+    cols, T = atlas_layout(n_faces, texels)
+    if side != T:
+        raise ValueError(f"the atlas of {int(n_faces)} faces at {texels} texels is {T} x {T}, the texture is "
+                         f"{side} x {side}")
+    return T, int(texture.shape[2])
+
+
+def mesh_texture_lookup(texture, texels, n_faces, face, bary, ranges_checked=False):
+    """The texture at points of the surface (nerf_mesh_texture_lookup): texture (T,T,C) float32 over
+    the atlas of (n_faces, texels), C in 1..4; face (N,) int32 and bary (N,2) float32 = (u, v) as mesh_ray_cast
+    returns them, the point being (1 - u - v) a + u b + v c of the face's corners.  Returns (N,C) float32: the bilinear
+    fetch at the face's own UV, written as lerps so that equal texels give their value exactly; zeros where face < 0.
+    A point of a face blends texels of that face's half cell only, gutter included (no bleeding between faces).
+    Bitwise reproducible.  ValueError before the launch on CPU tensors, wrong dtypes or shapes, a texture that is not
+    the atlas of (n_faces, texels), and a face >= n_faces (one host read, skipped with ``ranges_checked``)."""
+    F = int(n_faces)
+    T, C = _texture_arg(texture, F, texels)
+    if 3 * F >= 2 ** 31:
+        raise ValueError(f"3 * F must be below 2^31, got F = {F}")
+    need(face, "face", torch.int32)
+    need(bary, "bary")
+    if face.dim() != 1 or tuple(bary.shape) != (face.shape[0], 2):
+        raise ValueError(f"face must be (N,) and bary (N,2), got {tuple(face.shape)}, {tuple(bary.shape)}")
+    if face.device != texture.device or bary.device != texture.device:
+        raise ValueError("face and bary must be on the texture's device")
+    N = int(face.shape[0])
+    if N >= 2 ** 31:
+        raise ValueError("face must have fewer than 2^31 rows")
+    if N and not ranges_checked and int(face.max()) >= F:
+        raise ValueError(f"face must be below {F} (negative: no face), got {int(face.max())}")
+    out = torch.empty((N, C), dtype=F32, device=texture.device)
+    if N:
+        check(lib().nerf_mesh_texture_lookup(ptr(texture), T, C, F, texels, ptr(face), ptr(bary), N, ptr(out),
+                                             stream()), "nerf_mesh_texture_lookup")
+    return out
+
+
 # ------------------------------------------------------------------ optimiser
 
 

@@ -32,6 +32,11 @@ themselves (csrc/mesh_distance.hip).
 Ray casting on the device (csrc/mesh_raycast.hip): Mesh.ray_cast returns the nearest face every ray
 hits, through the same face grid, and Mesh.render the depth, mask, face, normal and colour images of a pinhole view,
 with depth in the ray parameter of ray_rendering.render_image.
+
+Texture baking on the device (csrc/mesh_texture.hip): Mesh.atlas gives every texel of a per-face
+texture atlas its surface point and normal, Mesh.bake_texture fills the texture from any colour function,
+Mesh.sample_texture and the "texture" image of Mesh.render fetch it by (face, barycentric pair), and save_obj writes a
+textured OBJ with its MTL and PNG: the colour detail no longer falls with the triangle count.
 """
 from __future__ import annotations
 
@@ -47,25 +52,33 @@ __all__ = ["Mesh", "density_lattice", "extract_mesh"]
 
 class Mesh:
     """vertices (V,3) float32, faces (F,3) int32, optional per-vertex normals (V,3) float32 and colours (V,3) float32
-    in [0,1]; device or host tensors."""
+    in [0,1]; device or host tensors.  Optionally a texture (T,T,3) float32 in [0,1] over the per-face atlas of
+    (F, texels), with texels the side of an atlas cell; bake_texture sets both."""
 
-    def __init__(self, vertices, faces, normals=None, colors=None):
+    def __init__(self, vertices, faces, normals=None, colors=None, texture=None, texels=None):
         if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
             raise ValueError(f"vertices (V,3) and faces (F,3) expected, got {tuple(vertices.shape)}, {tuple(faces.shape)}")
         if normals is not None and tuple(normals.shape) != tuple(vertices.shape):
             raise ValueError(f"normals must be {tuple(vertices.shape)}, got {tuple(normals.shape)}")
         if colors is not None and tuple(colors.shape) != tuple(vertices.shape):
             raise ValueError(f"colors must be {tuple(vertices.shape)}, got {tuple(colors.shape)}")
+        if (texture is None) != (texels is None):
+            raise ValueError("texture and texels go together")
         self.vertices, self.faces, self.normals, self.colors = vertices, faces, normals, colors
+        self.texture, self.texels = texture, texels
+        if texture is not None:
+            self._texture_side()
 
     def __repr__(self):
         colors = "" if self.colors is None else ", colors=True"  # a mesh without colours prints as it always has
+        texture = "" if self.texture is None else f", texture={self.texture.shape[0]}"  # and one without a texture too
         return (f"Mesh(V={self.vertices.shape[0]}, F={self.faces.shape[0]}, normals={self.normals is not None}"
-                f"{colors}, device={self.vertices.device})")
+                f"{colors}{texture}, device={self.vertices.device})")
 
     def cpu(self) -> "Mesh":
         return Mesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu(),
-                    None if self.colors is None else self.colors.cpu())
+                    None if self.colors is None else self.colors.cpu(),
+                    None if self.texture is None else self.texture.cpu(), self.texels)
 
     def _host(self):
         v = self.vertices.detach().cpu().numpy().astype("<f4")
@@ -103,7 +116,12 @@ class Mesh:
 
     def save_obj(self, path) -> None:
         """Wavefront OBJ: v lines (`v x y z r g b` with colours, the common extension), vn lines when there are normals,
-        1-based f lines (a//a with normals); %.9g keeps every float32 exactly."""
+        1-based f lines (a//a with normals); %.9g keeps every float32 exactly.  A textured mesh also gets vt lines,
+        three per face in the faces' order (u = x / T, v = 1 - y / T of atlas_uv), f lines a/t/n (a/t without normals),
+        `mtllib` and `usemtl`, and beside the OBJ a .mtl that names a .png of the same stem with the texture as
+        round(clamp(c,0,1) 255), row 0 on top."""
+        if self.texture is not None:
+            return self._save_textured_obj(path)
         v, f, n = self._host()
         c = self._host_colors()
         with open(path, "w") as fh:
@@ -119,6 +137,114 @@ class Mesh:
             fmt = "f %d//%d %d//%d %d//%d\n" if n is not None else "f %d %d %d\n"
             for i, j, k in (f + 1).tolist():
                 fh.write(fmt % ((i, i, j, j, k, k) if n is not None else (i, j, k)))
+
+    def _save_textured_obj(self, path) -> None:
+        import os
+
+        from PIL import Image
+        T = self._texture_side()
+        v, f, n = self._host()
+        c = self._host_colors()
+        uv = self.atlas_uv().detach().cpu().numpy().astype(np.float64).reshape(-1, 2)
+        path = os.fspath(path)
+        stem = os.path.splitext(path)[0]
+        name = os.path.basename(stem)
+        tex = self.texture.detach().cpu().numpy().astype("<f4")
+        png = np.rint(np.clip(np.nan_to_num(tex, nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+        Image.fromarray(np.ascontiguousarray(png)).save(stem + ".png")
+        with open(stem + ".mtl", "w") as fh:
+            fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+        with open(path, "w") as fh:
+            fh.write(f"mtllib {name}.mtl\n")
+            if c is None:
+                for x in v.tolist():
+                    fh.write("v %.9g %.9g %.9g\n" % tuple(x))
+            else:
+                for x in np.concatenate([v, c], 1).tolist():
+                    fh.write("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(x))
+            for x, y in uv.tolist():
+                fh.write("vt %.9g %.9g\n" % (x / T, 1.0 - y / T))
+            if n is not None:
+                for x in n.tolist():
+                    fh.write("vn %.9g %.9g %.9g\n" % tuple(x))
+            fh.write(f"usemtl {name}\n")
+            fmt = "f %d/%d/%d %d/%d/%d %d/%d/%d\n" if n is not None else "f %d/%d %d/%d %d/%d\n"
+            for t, (i, j, k) in enumerate((f + 1).tolist()):
+                t = 3 * t + 1
+                fh.write(fmt % ((i, t, i, j, t + 1, j, k, t + 2, k) if n is not None else (i, t, j, t + 1, k, t + 2)))
+
+    # ---- texture baking on the device (kernels.mesh_atlas_texels / mesh_texture_lookup)
+
+    def _texture_side(self) -> int:
+        """T of the mesh's own texture, after checking it against the atlas of (F, texels)."""
+        if self.texture is None:
+            raise ValueError("the mesh has no texture (Mesh.bake_texture)")
+        t = self.texture
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("texture must be a (T,T,3) float32 tensor")
+        if t.shape[0] != t.shape[1]:
+            raise ValueError(f"texture must be square, got {tuple(t.shape)}")
+        if t.device != self.vertices.device:
+            raise ValueError("texture must be on the mesh's device")
+        if isinstance(self.texels, bool) or not isinstance(self.texels, int) or self.texels < K.ATLAS_MIN_TEXELS:
+            raise ValueError(f"texels must be an int >= {K.ATLAS_MIN_TEXELS}, got {self.texels!r}")
+        if t.shape[0] % self.texels:
+            raise ValueError(f"texels = {self.texels} does not divide the texture's side {t.shape[0]}")
+        T = K.atlas_layout(self.faces.shape[0], self.texels)[1]
+        if t.shape[0] != T:
+            raise ValueError(f"the atlas of {self.faces.shape[0]} faces at {self.texels} texels is {T} x {T}, the "
+                             f"texture is {t.shape[0]} x {t.shape[0]}")
+        return T
+
+    def atlas(self, texels, normals=True) -> dict:
+        """kernels.mesh_atlas_texels on this mesh: for every texel [y, x] of the T x T atlas of (F, texels) the owning
+        "face" (-1: nobody's), the barycentric pair "bary", the surface "position" and (``normals``) the "normal"
+        there (the mix of the mesh's vertex normals if it has them, else the face's own), and "texels", "cols", "T"."""
+        return K.mesh_atlas_texels(self.vertices, self.faces, texels,
+                                   vertex_normals=self.normals if normals else None, normals=normals)
+
+    def atlas_uv(self, texels=None) -> torch.Tensor:
+        """(F,3,2) float32: the UV corners of every face in texel units of its atlas (x right, y down), for
+        ``texels`` (default: the mesh's own).  Small integers, a function of (F, texels) alone: the even face of a
+        cell has (1,1), (S-3,1), (1,S-3), the odd one (S-1,S-1), (3,S-1), (S-1,3), plus the cell's origin."""
+        S = self.texels if texels is None else texels
+        if S is None:
+            raise ValueError("the mesh has no texture: give texels")
+        F = int(self.faces.shape[0])
+        cols, _ = K.atlas_layout(F, S)
+        dev = self.faces.device
+        f = torch.arange(F, dtype=torch.int64, device=dev)
+        cell, odd = torch.div(f, 2, rounding_mode="floor"), (f % 2)[:, None]
+        origin = torch.stack([cell % cols, torch.div(cell, cols, rounding_mode="floor")], 1) * S  # (F, 2)
+        even = torch.tensor([[1, 1], [S - 3, 1], [1, S - 3]], dtype=torch.int64, device=dev)
+        local = torch.where(odd[:, :, None] == 1, S - even[None], even[None])  # (F, 3, 2)
+        return (local + origin[:, None, :]).to(torch.float32)
+
+    def bake_texture(self, color_fn: Callable, texels: int = 8, normals: bool = True) -> "Mesh":
+        """Fill this mesh's texture: ``color_fn``(points (M,3), normals (M,3)) -> (M,3) colours in [0,1] is called
+        once, on the surface points of the texels that a face owns (in the atlas's row order) and the normals there
+        (None with ``normals`` = False); the result is scattered into a (T,T,3) float32 texture, unowned texels are 0.
+        Sets .texture and .texels and returns self.  Gutter texels hold the colour of a nearby boundary point of
+        their own face, so a bilinear fetch anywhere on a face blends that face's colours only."""
+        a = self.atlas(texels, normals=normals)
+        T = a["T"]
+        idx = torch.nonzero(a["face"].reshape(-1) >= 0).reshape(-1)
+        texture = torch.zeros((T * T, 3), dtype=torch.float32, device=self.vertices.device)
+        if idx.numel():
+            pts = a["position"].reshape(-1, 3)[idx]
+            nrm = a["normal"].reshape(-1, 3)[idx] if normals else None
+            col = color_fn(pts, nrm)
+            if not isinstance(col, torch.Tensor) or tuple(col.shape) != (idx.numel(), 3):
+                raise ValueError(f"color_fn must return a tensor ({idx.numel()},3)")
+            texture[idx] = col.detach().to(device=texture.device, dtype=torch.float32)
+        self.texture, self.texels = texture.view(T, T, 3), texels
+        return self
+
+    def sample_texture(self, face, bary) -> torch.Tensor:
+        """kernels.mesh_texture_lookup on the mesh's own texture: face (N,) int32 and bary (N,2) float32 as ray_cast
+        returns them -> (N,3) float32, the bilinear fetch at the point's UV; zeros where face < 0."""
+        self._texture_side()
+        return K.mesh_texture_lookup(self.texture, self.texels, self.faces.shape[0], face, bary)
 
     # ---- clean-up on the device (kernels.mesh_components / mesh_compact, DESIGN §3.11.1)
 
@@ -248,10 +374,10 @@ class Mesh:
     def compute_normals(self) -> "Mesh":
         """The mesh with unit vertex normals derived from its faces: the normalised sum of the cross products of the
         faces around a vertex (area-weighted), by the faces' winding, which for an extracted mesh points to lower
-        density like every normal here; zeros at a vertex without a face.  Vertices, faces and colours are the same
-        tensors."""
+        density like every normal here; zeros at a vertex without a face.  Vertices, faces, colours and the texture
+        are the same tensors."""
         K._vertices_arg(self.vertices)
-        return Mesh(self.vertices, self.faces, self._face_normals(self.vertices), self.colors)
+        return Mesh(self.vertices, self.faces, self._face_normals(self.vertices), self.colors, self.texture, self.texels)
 
     def smooth(self, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, fixed=None) -> "Mesh":
         """Taubin smoothing: ``iterations`` times a Jacobi pass v += lam (mean of the neighbours - v) followed by one
@@ -419,7 +545,8 @@ class Mesh:
           face   (H,W) int32     the face, -1 where nothing is hit
           normal (H,W,3) float32 with vertex normals their barycentric mix, normalised; without them the unit normal of
                                  the face by its winding; zeros where nothing is hit
-          color  (H,W,3) float32 only for a mesh with colours: their barycentric mix, zeros where nothing is hit.
+          color  (H,W,3) float32 only for a mesh with colours: their barycentric mix, zeros where nothing is hit
+          texture (H,W,3) float32 only for a textured mesh: sample_texture at the hit, zeros where nothing is hit.
         The cast is Mesh.ray_cast; the gathers and mixes are a few float64 torch ops, rounded to fp32 at the end."""
         from .ray_sampling import rays_for_camera
         H, W = int(H), int(W)
@@ -437,6 +564,8 @@ class Mesh:
                    "normal": torch.zeros((H, W, 3), dtype=torch.float32, device=dev)}
             if self.colors is not None:
                 out["color"] = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+            if self.texture is not None:
+                out["texture"] = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
             return out
         corners = self.faces[face.clamp(min=0).to(torch.int64)].to(torch.int64)  # (n, 3); face 0 stands in at a miss
         u, v = bary[:, 0].to(torch.float64), bary[:, 1].to(torch.float64)
@@ -457,6 +586,8 @@ class Mesh:
             c = self.colors[corners]  # (n, 3 corners, 3): the mix stays between the corners' values per channel
             color = torch.minimum(torch.maximum(mix(self.colors).to(torch.float32), c.amin(1)), c.amax(1))
             out["color"] = (color * hit[:, None]).view(H, W, 3)
+        if self.texture is not None:
+            out["texture"] = self.sample_texture(face, bary).view(H, W, 3)  # a miss has face -1: zeros
         return out
 
 

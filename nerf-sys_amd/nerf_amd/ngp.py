@@ -32,6 +32,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from ._lib import check, lib, need, ptr, stream
+from .kernels import atlas_layout as _atlas_layout
 from .vanilla import VanillaNeRF
 
 _INTERP = {"Nearest": 0, "Linear": 1, "Smoothstep": 2}
@@ -796,7 +797,7 @@ class InstantNGP(nn.Module):
     def extract_mesh(self, resolution=256, threshold: float = 10.0, aabb=None, params=None, normals="field",
                      chunk: int = 2 ** 20, colors=None, min_faces=None, keep_largest=None, simplify=None,
                      smooth=None, simplify_placement="mean", method="tets", placement="qef", tol: float = 1e-3,
-                     hermite="field", refine: int = 0):
+                     hermite="field", refine: int = 0, texture=None):
         """The surface density = threshold as a mesh.Mesh on the device: self.density on a lattice of ``resolution``
         (an int or a triple) points over ``aabb`` (6 floats; default: the model's box), then marching tetrahedra
         (kernels.mesh_extract).  normals: "field" (self.normals at the vertices), "grid" (central differences of the
@@ -810,8 +811,12 @@ class InstantNGP(nn.Module):
         simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify (quadric-error vertices).
         method: "tets" or "dual" (dual contouring, mesh.extract_mesh); placement, tol and refine as there, for "dual"
         only.  hermite: the normals of dual contouring's crossing points, "field" (self.normals there, one fused
-        launch) or "grid" (the lattice's central differences); marching tetrahedra does not use it."""
+        launch) or "grid" (the lattice's central differences); marching tetrahedra does not use it.
+        texture: None, or the side in texels of an atlas cell: self.bake_texture on the final mesh as the last step,
+        in the colour space of ``colors`` ("srgb" where that is None)."""
         from .mesh import extract_mesh
+        if texture is not None:
+            _atlas_layout(0, texture)  # a bad side fails before the extraction
         if method not in ("tets", "dual"):
             raise ValueError(f'method must be "tets" or "dual", got {method!r}')
         if hermite not in ("field", "grid"):
@@ -833,12 +838,15 @@ class InstantNGP(nn.Module):
                             normals="grid" if normals == "grid" else None, chunk=chunk,
                             device=self.xyz_encoder.hash_table.device, min_faces=min_faces, keep_largest=keep_largest,
                             simplify=simplify, smooth=smooth, simplify_placement=simplify_placement, **dual)
-        return self._mesh_attributes(mesh, normals, colors, params, chunk)
+        mesh = self._mesh_attributes(mesh, normals, colors, params, chunk)
+        if texture is not None:
+            self.bake_texture(mesh, texture, colors=colors or "srgb", params=params, chunk=chunk)
+        return mesh
 
     def extract_mesh_tsdf(self, poses, H, W, fx, fy, cx, cy, near, far, resolution=256, aabb=None, trunc=None,
                           acc_min: float = 0.5, min_weight=1, normals="field", colors=None, min_faces=None,
                           keep_largest=None, simplify=None, smooth=None, params=None, chunk: int = 2 ** 20,
-                          batch: int = 8, simplify_placement="mean", **render_kwargs):
+                          batch: int = 8, simplify_placement="mean", texture=None, **render_kwargs):
         """The surface the cameras ``poses`` (n,3,4) see, as a mesh.Mesh on the device: render_image's depth from every
         pose, fused into a TSDF volume of ``resolution`` points over ``aabb`` (default: the model's box) by
         ray_rendering.fuse_depth_views (trunc, acc_min, batch, render_kwargs as there), then
@@ -846,7 +854,12 @@ class InstantNGP(nn.Module):
         as in extract_mesh: field normals and colours are evaluated at the surviving vertices.  colors="fused" instead
         fuses render_image's rgb alongside the depth and samples the volume's colour at the final vertices
         (fuse_depth_views(colors=True), TSDFVolume.extract_mesh(colors="fused")): the colours the cameras saw, with
-        no query of the colour network.  simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify."""
+        no query of the colour network.  simplify_placement: "mean" or "quadric", the ``placement`` of Mesh.simplify.
+        texture: None, or the side in texels of an atlas cell: the final mesh's texture is baked as the last step, with
+        colors="fused" from the volume (TSDFVolume.bake_texture), otherwise by self.bake_texture in the colour space of
+        ``colors`` ("srgb" where that is None)."""
+        if texture is not None:
+            _atlas_layout(0, texture)  # a bad side fails before any view is rendered
         if simplify_placement not in ("mean", "quadric"):
             raise ValueError(f'simplify_placement must be "mean" or "quadric", got {simplify_placement!r}')
         from .ray_rendering import fuse_depth_views
@@ -863,8 +876,33 @@ class InstantNGP(nn.Module):
                                colors=fused, params=params, **render_kwargs)
         mesh = vol.extract_mesh(min_weight=min_weight, normals="grid" if normals == "grid" else None,
                                 min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth,
-                                colors="fused" if fused else None, simplify_placement=simplify_placement)
-        return self._mesh_attributes(mesh, normals, None if fused else colors, params, chunk)
+                                colors="fused" if fused else None, simplify_placement=simplify_placement,
+                                texture=texture if fused else None)
+        mesh = self._mesh_attributes(mesh, normals, None if fused else colors, params, chunk)
+        if texture is not None and not fused:
+            self.bake_texture(mesh, texture, colors=colors or "srgb", params=params, chunk=chunk)
+        return mesh
+
+    def bake_texture(self, mesh, texels: int = 8, colors: str = "srgb", params=None, chunk: int = 2 ** 20):
+        """Fill ``mesh``'s texture atlas (Mesh.bake_texture; cells of ``texels`` x ``texels`` texels)
+        from the colour network: at the surface point of every owned texel the field normal (self.normals there) and
+        self.vertex_colors along it, the order _mesh_attributes uses for the vertices; colors: "linear" or "srgb"
+        (losses.linear_to_srgb of them).  Both run in chunks of ``chunk`` points; every row is evaluated on its own.
+        Returns the mesh, whose .texture and .texels are set."""
+        if colors not in ("linear", "srgb"):
+            raise ValueError(f"colors must be 'linear' or 'srgb', got {colors!r}")
+        if chunk < 1:
+            raise ValueError(f"chunk must be positive, got {chunk}")
+
+        def color_fn(points, _):
+            nrm = torch.cat([self.normals(points[s:s + chunk], params) for s in range(0, points.shape[0], chunk)])
+            rgb = self.vertex_colors(points, nrm, params, chunk=chunk)
+            if colors == "srgb":
+                from .losses import linear_to_srgb
+                rgb = linear_to_srgb(rgb)
+            return rgb
+
+        return mesh.bake_texture(color_fn, texels, normals=False)
 
     def _mesh_attributes(self, mesh, normals, colors, params, chunk):
         """field normals and colours at the vertices of ``mesh`` (extract_mesh, extract_mesh_tsdf)"""

@@ -8,7 +8,8 @@ which removes the sheet at -trunc behind every surface and everything the camera
 
 With color=True the volume also fuses the colour of the pixel each depth came from (kernels.tsdf_integrate_color,
 DESIGN §3.11.9), and extract_mesh(colors="fused") samples it at the final vertices (kernels.tsdf_sample_color): vertex
-colours for any source of views, with no model to query.
+colours for any source of views, with no model to query.  bake_texture fills a mesh's texture atlas from the same
+volume (Mesh.bake_texture), and extract_mesh(texture=TEXELS) does so as its last step.
 """
 from __future__ import annotations
 
@@ -86,7 +87,7 @@ class TSDFVolume:
     def extract_mesh(self, min_weight=1, normals: Optional[str] = "grid", min_faces: Optional[int] = None,
                      keep_largest: Optional[int] = None, simplify: Optional[float] = None,
                      smooth: Optional[int] = None, colors: Optional[str] = None,
-                     simplify_placement: str = "mean", method: str = "tets") -> Mesh:
+                     simplify_placement: str = "mean", method: str = "tets", texture: Optional[int] = None) -> Mesh:
         """The zero level of the fused field as a Mesh: mesh_extract(-tsdf, 0) (inside is tsdf < 0, normals point to
         larger tsdf: outwards), then only the faces of cells whose 8 corners all have weight >= min_weight
         (min_weight = 0 keeps every face, the sheet at -trunc behind the surface included), then the options of
@@ -94,7 +95,8 @@ class TSDFVolume:
         "fused" on a volume with colour: sample_colors at the final vertices, after the filters, simplify and smooth,
         as Mesh.colors (0.5 where no view coloured a corner of the vertex's cell).  simplify_placement: "mean" or
         "quadric", the ``placement`` of Mesh.simplify.  method: "tets" only; the observed-face filter maps a face to
-        the one cell that emitted it, and a quad of dual contouring spans four."""
+        the one cell that emitted it, and a quad of dual contouring spans four.  texture: None, or on a volume with
+        colour the side in texels of an atlas cell: bake_texture on the final mesh, as the last step."""
         if method != "tets":
             raise ValueError(f'TSDFVolume.extract_mesh supports method="tets" only, got {method!r}: its observed-face '
                              "filter needs one cell per face, and a dual-contouring quad spans four cells")
@@ -106,6 +108,10 @@ class TSDFVolume:
             raise ValueError(f"colors must be 'fused' or None, got {colors!r}")
         if colors == "fused" and self.color is None:
             raise ValueError("colors='fused' needs a volume with colour: TSDFVolume(..., color=True)")
+        if texture is not None:
+            if self.color is None:
+                raise ValueError("texture needs a volume with colour: TSDFVolume(..., color=True)")
+            K.atlas_layout(0, texture)  # a bad side fails before the extraction
         if smooth is not None and (isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0):
             raise ValueError(f"smooth must be None or an int >= 0, got {smooth!r}")
         if min_faces is not None and keep_largest is not None:
@@ -123,4 +129,16 @@ class TSDFVolume:
             mesh = mesh.smooth(smooth)
         if colors == "fused":
             mesh.colors = self.sample_colors(mesh.vertices)[0]
+        if texture is not None:
+            self.bake_texture(mesh, texture)
         return mesh
+
+    def bake_texture(self, mesh: Mesh, texels: int = 8, fill: float = 0.5) -> Mesh:
+        """Fill ``mesh``'s texture atlas (Mesh.bake_texture, cells of ``texels`` x ``texels`` texels) with the fused
+        colour: sample_colors at the surface point of every owned texel, ``fill`` where no view coloured a corner of
+        the point's cell.  The colours the cameras saw, for any source of views.  Returns the mesh."""
+        if self.color is None:
+            raise ValueError("bake_texture needs a volume with colour: TSDFVolume(..., color=True)")
+        if not isinstance(mesh, Mesh):
+            raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
+        return mesh.bake_texture(lambda p, n: self.sample_colors(p, fill)[0], texels, normals=False)

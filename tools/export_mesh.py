@@ -85,6 +85,15 @@ lattice edge with the density itself.  Every option and report above works on th
 cell per face.
 
   python tools/export_mesh.py --train-steps 2000 --method dual --dual-refine 4 --report-depth 4 --out mesh.ply
+
+--texture TEXELS (off by default; the files and every JSON line are unchanged without it) bakes a texture over a
+per-face atlas with cells of TEXELS x TEXELS texels as the last step of the extraction and writes a
+textured OBJ to --out, with FILE.mtl and FILE.png beside it: the colour detail then no longer falls with the triangle
+count, so it pairs with --simplify and --method dual.  The texture takes the colour space of --colors (srgb where that
+is none; fused bakes from the TSDF volume).  --out must not be a .ply, which carries no texture coordinates.  The first
+JSON line gains "texture" and "texture_side".
+
+  python tools/export_mesh.py --train-steps 2000 --simplify 0.02 --texture 8 --out mesh.obj
 """
 import argparse
 import json
@@ -153,6 +162,8 @@ def main():
                     help="--method dual: normals of the crossing points from the field's gradient or the lattice's")
     ap.add_argument("--dual-refine", type=int, default=0, metavar="N",
                     help="--method dual: bisection steps of every crossing point along its lattice edge")
+    ap.add_argument("--texture", type=int, default=None, metavar="TEXELS",
+                    help="bake a texture with TEXELS x TEXELS texels per pair of faces and write OBJ, MTL and PNG to --out")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--obj", default=None, help="also write a Wavefront OBJ here")
     a = ap.parse_args()
@@ -160,6 +171,12 @@ def main():
         ap.error("--colors fused needs --tsdf VIEWS: the colours are fused from the rendered views")
     if a.method == "dual" and a.tsdf:
         ap.error("--method dual does not combine with --tsdf: its observed-face filter needs one cell per face")
+    if a.texture is not None:
+        if a.out.lower().endswith(".ply"):
+            ap.error(f"--texture writes a textured OBJ with its MTL and PNG: give --out FILE.obj, not {a.out!r} "
+                     "(a PLY carries no texture coordinates)")
+        if a.texture < 5:
+            ap.error("--texture needs at least 5 texels: a cell holds two triangles and their gutter")
     dual = dict(method="dual", placement=a.dual_placement, hermite=a.dual_hermite, refine=a.dual_refine) \
         if a.method == "dual" else {}
     if not torch.cuda.is_available():
@@ -206,10 +223,13 @@ def main():
     t0 = time.perf_counter()
     mesh = extract(normals=None if a.normals == "none" else a.normals, colors=None if a.colors == "none" else a.colors,
                    min_faces=a.min_faces, keep_largest=a.keep_largest, simplify=a.simplify, smooth=a.smooth,
-                   simplify_placement=a.simplify_placement)
+                   simplify_placement=a.simplify_placement, **({} if a.texture is None else {"texture": a.texture}))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    mesh.save_ply(a.out)
+    if a.texture is None:
+        mesh.save_ply(a.out)
+    else:
+        mesh.save_obj(a.out)
     if a.obj:
         mesh.save_obj(a.obj)
     # for the report only (outside the timed call): the unfiltered surface and its components
@@ -228,6 +248,7 @@ def main():
                       "extract_seconds": round(dt, 4), "out": a.out,
                       **({"simplify_placement": a.simplify_placement} if a.simplify_placement != "mean" else {}),
                       **({"tsdf": a.tsdf, "tsdf_min_weight": a.tsdf_min_weight} if a.tsdf else {}),
+                      **({"texture": a.texture, "texture_side": int(mesh.texture.shape[0])} if a.texture else {}),
                       **({"method": "dual", "dual_placement": a.dual_placement, "dual_hermite": a.dual_hermite,
                           "dual_refine": a.dual_refine} if dual else {})}))
     if a.report_error:
