@@ -581,6 +581,14 @@ __device__ __forceinline__ ngp_f32x16 zero16() {
   return z;
 }
 
+// trunc_exp (models/trunc_exp.py:30-61) of the sigma head, value and gradient alike: exp(clamp(x, -c, c)), c =
+// 88.722839111.  In fp32 c rounds to 0x1.62e430p+6 > ln(FLT_MAX) = 88.72283905, where expf overflows: a saturated row
+// would carry sigma = +inf, and 0 * inf = NaN from a zero upstream gradient would reach every weight gradient.  The
+// exact exp(c) is FLT_MAX (1 + 5.9e-8), so the overflow is capped at FLT_MAX; every x below ln(FLT_MAX) is untouched.
+__device__ __forceinline__ float ngp_trunc_exp(float x) {
+  return fminf(expf(fminf(fmaxf(x, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX)), __FLT_MAX__);
+}
+
 // Y = act(X W^T + b) for one 64-row tile.  Lane li of wave (rb, cb) owns row rb*32+li; register 4q+e of its
 // accumulator is column cb*32 + 8q + 4lh + e (C^T tile: the weight is the MFMA's A operand).
 __device__ __forceinline__ void layer_fwd(const NgpLayer& L, float* smem, const float* __restrict__ w, int wave,
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(256) void ngp_fwd_kernel(NgpPlan P, const float* __
       const float sr = P.sraw >= 0 ? smem[P.sraw + r] : smem[P.ly[P.head].out_buf + r * P.ly[P.head].out_ld];
       float c0 = o[0], c1 = o[1], c2 = o[2];
       if (P.sigmoid) { c0 = nerf_mlp::sigmoidf_(c0); c1 = nerf_mlp::sigmoidf_(c1); c2 = nerf_mlp::sigmoidf_(c2); }
-      const float sg = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+      const float sg = ngp_trunc_exp(sr);
       reinterpret_cast<float4*>(out)[m] = make_float4(c0, c1, c2, sg);
     }
   }
@@ -728,7 +736,7 @@ __global__ __launch_bounds__(256) void ngp_density_kernel(NgpPlan P, const float
     const int64_t m = m0 + threadIdx.x;
     if (m < M) {
       const float sr = smem[P.ly[P.head].out_buf + threadIdx.x * P.ly[P.head].out_ld];
-      sigma[m] = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+      sigma[m] = ngp_trunc_exp(sr);
     }
   }
 }
@@ -1013,7 +1021,7 @@ __global__ __launch_bounds__(256, 2) void ngp_bwd_kernel(NgpPlan P, const float*
             }
             gq = make_float4(gc[0], gc[1], gc[2], 0.f);
             const float sr = smem[Lh.out_buf + pr * Lh.out_ld];
-            dsig[pr] = gv.w * expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+            dsig[pr] = gv.w * ngp_trunc_exp(sr);
           }
           lds_barrier();  // the raw head/out tiles alias the gradient tiles
           *reinterpret_cast<float4*>(smem + P.g0 + pr * 68 + 4 * pp) = gq;
@@ -1353,7 +1361,7 @@ __global__ __launch_bounds__(256, 2) void ngp_bwd_prod_kernel(const float* __res
               gq = make_float4(gv.x, gv.y, gv.z, 0.f);
             }
             const float sr = smem[G0 + pr * 68];
-            smem[DSIG + pr] = gv.w * expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+            smem[DSIG + pr] = gv.w * ngp_trunc_exp(sr);
           }
           lds_barrier();  // the raw head / rgb tiles alias the gradient tiles
           *reinterpret_cast<float4*>(smem + G0 + pr * 68 + 4 * pp) = gq;
@@ -1555,7 +1563,7 @@ __global__ __launch_bounds__(256) void ngp_fwd_prod_kernel(const float* __restri
   if constexpr (MODE == 1) {
     if (pp == 0 && ok) {
       const float sr = smem[F_PA + pr * 68];
-      out[m] = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+      out[m] = ngp_trunc_exp(sr);
     }
     return;
   } else {
@@ -1579,7 +1587,7 @@ __global__ __launch_bounds__(256) void ngp_fwd_prod_kernel(const float* __restri
       const float* o = smem + F_PB + pr * 68;
       float c0 = o[0], c1 = o[1], c2 = o[2];
       if (SIGMOID) { c0 = nerf_mlp::sigmoidf_(c0); c1 = nerf_mlp::sigmoidf_(c1); c2 = nerf_mlp::sigmoidf_(c2); }
-      const float sg = expf(fminf(fmaxf(smem[F_SRAW + pr], -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+      const float sg = ngp_trunc_exp(smem[F_SRAW + pr]);
       reinterpret_cast<float4*>(out)[m] = make_float4(c0, c1, c2, sg);
     }
   }
@@ -1633,7 +1641,7 @@ __global__ __launch_bounds__(256) void ngp_density_enc_prod_kernel(HashArgs a, c
   lds_barrier();
   if (tid < NGP_BROWS && m0 + tid < M) {
     const float sr = smem[F_PA + tid * 68];
-    sigma[m0 + tid] = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+    sigma[m0 + tid] = ngp_trunc_exp(sr);
   }
 }
 
@@ -1700,7 +1708,7 @@ __global__ __launch_bounds__(256) void ngp_density_grad_prod_kernel(HashArgs a, 
     // 8 pp .. 8 pp + 7 of h1
     const int pr = tid >> 3, pp = tid & 7;
     const float sr = smem[D_HD + pr * 68];
-    const float ds = expf(fminf(fmaxf(sr, -nerf_mlp::EXP_MAX), nerf_mlp::EXP_MAX));
+    const float ds = ngp_trunc_exp(sr);
     if (pp == 0 && m0 + pr < M) sigma[m0 + pr] = ds;
     const float4 w0 = *reinterpret_cast<const float4*>(w + WOFF[HEAD] + 8 * pp);
     const float4 w1 = *reinterpret_cast<const float4*>(w + WOFF[HEAD] + 8 * pp + 4);
